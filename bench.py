@@ -27,10 +27,28 @@ synthesis of one unit.  The timed region is unchanged: the K steps (one replay o
 captured pipeline) between barrier + synchronize.  The kernel-event region that feeds
 ``roofline`` runs the steps one at a time (pair 0).
 
-Rank 0 prints one JSON line with the throughput, the roofline of the dominant kernel
-(HIP events on the library's launch stream, algorithmic bytes per launch) and, at N=1,
-the CPU baseline (the NumPy oracle on a bounded sample, on one core and on all the
-host cores the box gives this process).
+A plain run (``bench.py --gpus N --steps K --warmup W``) does only what the headline needs:
+it sets up, runs the W warm-up steps, times the K steps, writes the outputs of the last
+timed step if ``--dump-outputs DIR`` is given, and rank 0 prints one JSON line with the
+throughput (``value``, ``ms_per_step``) and the configuration.
+
+``--full`` adds every secondary measurement to that line: the K steps one at a time
+(``ms_per_step_serial``), the roofline of the dominant kernel (HIP events on the library's
+launch stream, algorithmic bytes per launch, the device-copy rate) and, at N=1, the CPU
+baseline (the NumPy oracle on a bounded sample, on one core and on all the host cores the
+box gives this process), the standalone synthesis (``synthesis_only``) and BASELINE C3
+(``c3``).  ``--c3 0``, ``--synthesis-only 0``, ``--no-cpu-baseline`` and ``--kernel-events 0``
+switch single legs of a ``--full`` run off; without ``--full`` none of them runs.
+
+``--dump-outputs DIR``: after the timed region every rank writes what the last timed step
+left in its caller-visible buffers — the channelised product and the synthesised series of
+the plan pair that step ran on — as ``DIR/chan.npy`` and ``DIR/out.npy`` (``_rank<r>``
+appended to the names at N > 1), float32 arrays of shape (n_pol, S, 2) = (re, im).  An
+array of more than S complex samples per polarisation is sampled at S fixed positions
+(``dump_positions``: sorted draws of NumPy's default_rng(``DUMP_SEED``), the same in every
+run); S is chosen so that all files together stay under 64 MB.  The inputs depend on the
+arguments alone (one torch generator seed per unit), so two builds run with the same
+arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -64,11 +82,19 @@ def parse():
     ap.add_argument("--stub-device", action="store_true",
                     help="test hook: replace the device step by a CPU no-op and use gloo "
                          "(exercises the launcher, unit mapping and aggregation without a GPU)")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (K >= 1)")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed warm-up steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (CPU baseline, one-at-a-time steps, "
+                         "per-kernel events and roofline, device-copy rate, synthesis_only, c3); "
+                         "a run without it times the K steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (channelised product and "
+                         "synthesised series, a fixed seeded sample of each) as DIR/<name>.npy")
     ap.add_argument("--n-dat", type=int, default=N_DAT)
     ap.add_argument("--n-pol", type=int, default=0, help="override the workload's pols per rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full only: leave the CPU legs out")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--chunk-blocks", type=int, default=0)
     ap.add_argument("--graph", type=int, default=1,
@@ -91,24 +117,27 @@ def parse():
                     help="with --inflight D > 1: every plan pair reads its own synthetic units "
                          "(seeds + 7919 p), so overlapping steps share no input data")
     ap.add_argument("--kernel-events", type=int, default=1,
-                    help="record HIP events around every kernel in the timed region")
+                    help="--full only: record HIP events around every kernel in a region of its own")
     ap.add_argument("--stage1", choices=("auto", "stored", "recomputed"), default="auto",
                     help="synthesis stage-1 rows of the fused round trip "
                          "(pfb_synthesis_set_stage1_rows): written by the analysis and read back, "
                          "or recomputed from the input by the synthesis (bit-identical output)")
     ap.add_argument("--c3", type=int, default=1,
-                    help="N=1 only: also time BASELINE configs[2] (C3 SKA-Mid padded round trip, "
+                    help="--full, N=1 only: also time BASELINE configs[2] (C3 SKA-Mid padded round trip, "
                          "4096 ch, 100 353 taps, 2^26 samples) as the line's `c3` key (not the "
                          "headline value)")
     ap.add_argument("--synthesis-only", type=int, default=1,
-                    help="N=1 only: also time the standalone synthesis of an HBM-resident C2 "
+                    help="--full, N=1 only: also time the standalone synthesis of an HBM-resident C2 "
                          "channelised product (SynthesisPlan.execute: channel IFFT + synthesis, "
                          "the PST InverseFilterBank case) as the line's `synthesis_only` key")
     ap.add_argument("--e2e", type=int, default=0,
                     help="also time the host-buffer path: pinned DADA bytes (NBIT 8 TFP) -> "
                          "H2D -> unpack -> round trip -> pack (NBIT 32) -> D2H (reported as "
                          "e2e_pcie; never the headline value)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 CPU_UNIT = 1 << 20  # samples per CPU-baseline unit (a bounded sample of the C2 workload)
@@ -424,14 +453,14 @@ def main():
     seeds = (seeds * n_pol)[:n_pol] if args.n_pol else seeds
     n_dat = args.n_dat
 
-    # CPU baseline first (rank 0, N = 1), before this process touches the GPU: its
+    # CPU baseline first (--full, rank 0, N = 1), before this process touches the GPU: its
     # worker processes are forked from a process with no device state
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds, args.cpu_workers or cpu_workers_default())
-    # C3 (N = 1 only): its taps (plan-time firls design, a few seconds) and its CPU leg
+    # C3 (--full, N = 1 only): its taps (plan-time firls design, a few seconds) and its CPU leg
     c3 = None
-    if world == 1 and args.c3 and not args.stub_device:
+    if args.full and world == 1 and args.c3 and not args.stub_device:
         c3 = {"taps": c3_taps()}
         if not args.no_cpu_baseline:
             c3["cpu_baseline"] = cpu_baseline_c3(c3["taps"])
@@ -502,8 +531,9 @@ def run_stub(args, world, dist):
     for _ in range(args.warmup):
         step()
     el = timed_region(args.steps, step, world, dist, lambda: None)
-    return {"el": el, "el_prof": el, "el_serial": el, "kern": {}, "copy_gbs": None, "e2e": None,
-            "taps": 3073, "K": 0, "n_out": 0}
+    sec = el if args.full else None  # the secondary regions are --full's
+    return {"el": el, "el_prof": sec, "el_serial": sec, "kern": {} if args.full else None,
+            "copy_gbs": None, "e2e": None, "taps": 3073, "K": 0, "n_out": 0}
 
 
 PROFILE_CLASSES = ["analysis", "synth_chan_ifft", "synth_block", "analysis+chan_ifft", "fir", "row_fft"]
@@ -769,16 +799,23 @@ def run_device(args, torch, dist, world, rank, local, n_pol, n_dat, seeds, c3=No
         pairs.append((ana, syn, chan_buf, out_buf))
     ana, syn, chan_buf, out_buf = pairs[0]
 
-    def make_step(ana, syn, chan_buf, out_buf, x):
+    # what a caller of pair p's step receives: (channelised product, synthesised series).  The
+    # round-trip calls fill the pair's own buffers; the separate calls (--roundtrip 0) return
+    # theirs (under a graph: the tensors of the capturing call, which every replay refills)
+    returned = [(p[2], p[3]) for p in pairs]
+
+    def make_step(i, ana, syn, chan_buf, out_buf, x):
         def step_serial():
             chan = ana.execute(x)            # (n_pol, K, N) time-major channelised data
-            return syn.execute(chan, layout="ptc")
+            out = syn.execute(chan, layout="ptc")
+            returned[i] = (chan, out)
+            return out
 
         def step_pipelined():
             return pfb.roundtrip(ana, syn, x, chan=chan_buf, out=out_buf)
         return step_pipelined if args.roundtrip else step_serial
 
-    steps_of = [make_step(*p, inputs[i]) for i, p in enumerate(pairs)]
+    steps_of = [make_step(i, *p, inputs[i]) for i, p in enumerate(pairs)]
     step = steps_of[0]
 
     lib = _lib.load()
@@ -823,6 +860,18 @@ def run_device(args, torch, dist, world, rank, local, n_pol, n_dat, seeds, c3=No
         el = timed_region(1, batch, world, dist, sync)  # one replay = the K steps
     else:
         el = timed_region(args.steps, run, world, dist, sync)
+    if args.dump_outputs:
+        # step K-1 ran on plan pair (K-1) mod D
+        dump_outputs(args.dump_outputs, returned[(args.steps - 1) % D], rank, world)
+    res = {"el": el, "el_prof": None, "el_serial": None, "kern": None, "copy_gbs": None,
+           "e2e": None, "taps": len(taps), "K": K, "n_out": n_out, "synthesis_only": None,
+           "c3": None}
+    if not args.full:
+        if args.e2e:
+            res["e2e"] = e2e_pcie(torch, dev, pfb, ana, syn, n_pol, n_dat, chan_buf, out_buf,
+                                  args.steps, world, dist)
+        return res
+
     # the same K steps one at a time on one stream (pair 0, D = 1): ms_per_step_serial
     el_serial = el if D == 1 else timed_region(args.steps, runs[0], world, dist, sync)
     # profiled region: the same K steps with HIP events recorded around every kernel
@@ -885,15 +934,44 @@ def run_device(args, torch, dist, world, rank, local, n_pol, n_dat, seeds, c3=No
         c3_res["dual_pol"] = measure_c3(args, torch, dist, world, dev, pfb, lib, c3, n_pol=2)
         if "cpu_baseline" in c3:
             c3_res["cpu_baseline"] = c3["cpu_baseline"]
-    return {"el": el, "el_prof": el_prof, "el_serial": el_serial, "kern": kern, "copy_gbs": copy_gbs,
-            "e2e": e2e, "taps": len(taps), "K": K, "n_out": n_out, "synthesis_only": syn_only,
-            "c3": c3_res}
+    res.update(el_prof=el_prof, el_serial=el_serial, kern=kern, copy_gbs=copy_gbs, e2e=e2e,
+               synthesis_only=syn_only, c3=c3_res)
+    return res
+
+
+DUMP_SEED = 20240229
+DUMP_BYTES = 32 << 20  # all of a run's .npy payloads together (the limit is 64 MB)
+
+
+def dump_positions(n: int, s: int):
+    """The s positions of an n-sample series that --dump-outputs keeps: all of them if
+    n <= s, else s sorted draws (with replacement) of default_rng(DUMP_SEED)."""
+    if n <= s:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=s, dtype=np.int64))
+
+
+def dump_outputs(path, arrays, rank: int, world: int):
+    """Write (chan, out) — the (n_pol, K, N) channelised product and the (n_pol, n_out)
+    synthesised series the last timed step left with its caller — as float32 (n_pol, S, 2)
+    arrays path/chan.npy and path/out.npy (module docstring)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    for name, t in zip(("chan", "out"), arrays):
+        flat = t.reshape(t.shape[0], -1)
+        s = DUMP_BYTES // (8 * len(arrays) * world * flat.shape[0])
+        pos = torch.from_numpy(dump_positions(flat.shape[1], s)).to(flat.device)
+        kept = torch.view_as_real(flat.index_select(1, pos).contiguous()).cpu().numpy()
+        np.save(os.path.join(path, f"{name}{tag}.npy"), kept.astype(np.float32, copy=False))
 
 
 def report(args, res, world, workload, n_pol, n_dat, all_seeds):
     el, kern = res["el"], res["kern"]
     samples = world * n_pol * n_dat * args.steps
     value = samples / el / 1e6
+    secondary = kern is not None  # the --full regions ran
+    kern = kern or {}
     if kern:
         dom = max(kern, key=lambda k: kern[k]["avg_ms"] * kern[k]["launches"])
         kd = kern[dom]
@@ -902,7 +980,7 @@ def report(args, res, world, workload, n_pol, n_dat, all_seeds):
         dom, achieved = None, 0.0
     kname = kern[dom].get("kernel") if dom else None
     traffic, why = traffic_for(workload, kname, pmc_traffic()) if dom else (None, "no kernel timed")
-    if why and not args.stub_device:
+    if why and secondary and not args.stub_device:
         print(f"bench.py: WARNING roofline.traffic unavailable: {why}", file=sys.stderr, flush=True)
     roof = {"bound": "hbm", "kernel": kernel_key(kname) or dom, "kernel_class": dom,
             "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -925,7 +1003,7 @@ def report(args, res, world, workload, n_pol, n_dat, all_seeds):
         "warmup": args.warmup,
         "ms_per_step": round(el / args.steps * 1e3, 4),
         # the same K steps one at a time on one stream (no step in flight beside another)
-        "ms_per_step_serial": round(res.get("el_serial", el) / args.steps * 1e3, 4),
+        "ms_per_step_serial": round((res.get("el_serial") or el) / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -949,9 +1027,13 @@ def report(args, res, world, workload, n_pol, n_dat, all_seeds):
                    "stage1_rows": getattr(args, "stage1", "auto")},
         "roofline": roof,
         "round_trip_hbm_frac": round(rt_gbs / HBM_PEAK_GBS, 4),
-        "ms_per_step_with_kernel_events": round(res["el_prof"] / args.steps * 1e3, 4),
+        "ms_per_step_with_kernel_events": round((res.get("el_prof") or el) / args.steps * 1e3, 4),
         "kernels": kern,
     }
+    out["full"] = secondary
+    if not secondary:  # a plain run measured none of these: the line does not carry them
+        for key in ("ms_per_step_serial", "roofline", "ms_per_step_with_kernel_events", "kernels"):
+            del out[key]
     traffic_all = pmc_traffic()
 
     def with_traffic(kc, wl):

@@ -73,18 +73,55 @@ def test_gpus_2_launches_two_ranks_and_aggregates():
 
 
 def test_gpus_1_is_the_c2_headline():
-    r = _run(["--stub-device", "--steps", "2", "--warmup", "0", "--no-cpu-baseline"])
+    r = _run(["--stub-device", "--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 1
     assert d["config"]["workload"].startswith("C2")
     assert d["config"]["unit_seeds_per_rank"] == [[100, 8019, 15938]]
     assert d["config"]["units_in_flight"] == 3
-    assert d["ms_per_step_serial"] > 0
+    assert d["full"] is True and d["ms_per_step_serial"] > 0
     r = _run(["--stub-device", "--steps", "2", "--warmup", "0", "--no-cpu-baseline",
               "--inflight", "1"])
     d = _json_line(r.stdout)
     assert d["config"]["unit_seeds_per_rank"] == [[100]] and d["config"]["units_in_flight"] == 1
+
+
+def test_plain_run_times_the_steps_and_nothing_else():
+    """Without --full the line carries the headline (value from ms_per_step and --steps) and
+    none of the secondary measurements: no CPU baseline, serial region, kernel events,
+    roofline, synthesis_only or c3."""
+    steps = 3
+    r = _run(["--gpus", "1", "--stub-device", "--steps", str(steps), "--warmup", "1"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    assert d["full"] is False and d["steps"] == steps and d["warmup"] == 1
+    assert d["metric"] == "complex Msamples/s PFB analysis->synthesis"
+    assert d["unit"] == "complex Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    # the stubbed step waits 2 ms
+    assert 2.0 <= d["ms_per_step"] < 50.0
+    samples = d["config"]["n_dat_per_unit"] * steps
+    assert abs(d["value"] - samples / (d["ms_per_step"] * steps / 1e3) / 1e6) / d["value"] < 1e-3
+    assert d["cpu_baseline"] is None
+    for key in ("ms_per_step_serial", "roofline", "kernels", "ms_per_step_with_kernel_events",
+                "synthesis_only", "c3"):
+        assert key not in d, key
+
+
+def test_steps_must_be_positive():
+    r = _run(["--stub-device", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_positions_are_fixed_and_bounded():
+    """--dump-outputs keeps a whole short series and the same sorted sample of a long one."""
+    import numpy as np
+    assert bench.dump_positions(5, 8).tolist() == [0, 1, 2, 3, 4]
+    a, b = bench.dump_positions(1 << 24, 1 << 10), bench.dump_positions(1 << 24, 1 << 10)
+    assert a.dtype == np.int64 and a.shape == (1 << 10,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) >= 0) and 0 <= a[0] and a[-1] < 1 << 24
+    # everything a run writes stays under the 64 MB limit: 2 arrays x world x n_pol x S x 8 B
+    assert bench.DUMP_BYTES <= 64 << 20
 
 
 def test_gpus_must_match_launcher_world():
