@@ -648,10 +648,20 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
                                   pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out, int32_t mem,
                                   void* stream, const OutLayout* lay) {
   if (!p || (!in && n_in > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
+  if (n_in < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_in");
   HIPCHK(hipSetDevice(p->device));
   hipStream_t s = (hipStream_t)stream;
   const int64_t total = p->buffered + n_in;
   const hipMemcpyKind kin = mem == PFB_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  if (mem == PFB_MEM_DEVICE) {
+    // the strides of device buffers are the caller's: checked like pfb_analysis_execute's,
+    // before any state changes (`lay`: out_ps belongs to the strided layout, range-checked
+    // by pfb_filterbank_execute_strided)
+    const int64_t K0 = analysis_K(p, total);
+    const int64_t Kt0 = K0 - (K0 % p->nu);
+    if (in_ps < n_in || (!lay && out_ps < Kt0 * p->C))
+      return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
+  }
   {
     // Carry without the concatenation copy (streaming analysis kernel, device input):
     // rows k >= ceil(B / M) read only the new input, so they run on it in place with the
@@ -738,7 +748,9 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
       const int64_t Krun = p->variant == pfb::kPadded ? K : Kt;
       float2* dst = (float2*)out;
       int64_t dps = out_ps;
-      if (Krun > cap) {
+      // (the scratch rows [Kt, Krun) need room in the pol's own stride too: pols packed
+      // closer than Krun rows would have them land on the next pol's first rows)
+      if (Krun > cap || out_ps < Krun * p->C) {
         HIPCHK(p->stage_out.ensure((size_t)p->n_pol * Krun * p->C * sizeof(float2)));
         dst = p->stage_out.as<float2>();
         dps = Krun * p->C;
@@ -797,10 +809,11 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
       dst = (float2*)out;
       dps = out_ps;
       // padded: K rows computed (the circular shift spans all of them), Kt returned; they go
-      // straight into the caller's buffer when it has room for K rows (rows [Kt, K) are then
-      // scratch, pfb_filterbank_execute's contract), else through a staging buffer and a copy
+      // straight into the caller's buffer when it has room for K rows in the capacity and in
+      // each pol's stride (rows [Kt, K) are then scratch, pfb_filterbank_execute's contract),
+      // else through a staging buffer and a copy
       // (round 6: the SKA-Mid cascade's stage 2 lost a 244-us copy per call)
-      if (Krun > cap) {
+      if (Krun > cap || (!lay && out_ps < Krun * p->C)) {
         HIPCHK(p->stage_out.ensure((size_t)p->n_pol * Krun * p->C * sizeof(float2)));
         dst = p->stage_out.as<float2>();
         dps = Krun * p->C;
@@ -1422,6 +1435,7 @@ pfb_status pfb_synthesis_execute(pfb_synthesis_plan* p, const pfb_cf32* in, int6
                                  void* stream) {
   if (!p || (!in && n_dat > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
   if (sample_offset < 1) return fail(PFB_ERR_INVALID_ARG, "sample_offset is 1-based (>= 1)");
+  if (n_dat < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_dat");
   HIPCHK(hipSetDevice(p->device));
   hipStream_t s = (hipStream_t)stream;
   const int64_t off = std::min<int64_t>(sample_offset - 1, std::max<int64_t>(n_dat, 0));
@@ -1497,6 +1511,8 @@ pfb_status pfb_inverse_filterbank_execute(pfb_synthesis_plan* p, const pfb_cf32*
   if (n_out) *n_out = olen;
   if (olen > cap) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld",
                               (long long)cap, (long long)olen);
+  if (mem == PFB_MEM_DEVICE && (in_ps < n_in * N || out_ps < olen))
+    return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
   {
     // Carry without the concatenation copy: blocks whose rows start at or after the
     // carried Bc rows read the new input in place (row shift Bc - so), the first ones a

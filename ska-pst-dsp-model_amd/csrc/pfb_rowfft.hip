@@ -238,8 +238,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3))) void ro
   const uint32_t lane_0 = REV ? (tid ? (uint32_t)(N - tid) * ES : 0u) : lane_a;
   v4u pf[16];
   auto load_pair = [&](int64_t pp) {
-    // (!RUN: the last pair of an odd row count has no row B — its loads leave the range)
-    const uint32_t nrec = RUN ? (uint32_t)(N * 16) : (2 * pp + 1 < a.n_rows ? 2u : 1u) * (uint32_t)(N * 8);
+    // (!RUN: the last pair of an odd row count has no row B.  Row B's displacement rides in
+    // the scalar offset, which the descriptor's range check does not cover — it compares the
+    // lane offset alone, pfb_synth_wave.hpp — so a one-row descriptor would not drop those
+    // loads: they would read the 32 KB after the last row.  They are pointed at row A
+    // instead: row_b = 0, a uniform scalar; the values are never transformed.)
+    const bool has_b = RUN || 2 * pp + 1 < a.n_rows;
+    const uint32_t nrec = RUN ? (uint32_t)(N * 16) : (has_b ? 2u : 1u) * (uint32_t)(N * 8);
+    [[maybe_unused]] const int row_b = has_b ? N * 8 : 0;
     const __amdgpu_buffer_rsrc_t rs = make_rsrc_u(in + pp * 2 * N, nrec);
     static_for<0, 16>([&](auto rv) {
       constexpr int r = decltype(rv)::value;
@@ -249,7 +255,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3))) void ro
         pf[r] = __builtin_amdgcn_raw_buffer_load_b128(rs, lo, soff, kNtlRow ? 2 : 0);
       } else {
         const v2u x0 = __builtin_amdgcn_raw_buffer_load_b64(rs, lo, soff, kNtlRow ? 2 : 0);
-        const v2u x1 = __builtin_amdgcn_raw_buffer_load_b64(rs, lo, soff + N * 8, kNtlRow ? 2 : 0);
+        const v2u x1 = __builtin_amdgcn_raw_buffer_load_b64(rs, lo, soff + row_b, kNtlRow ? 2 : 0);
         pf[r] = v4u{x0.x, x0.y, x1.x, x1.y};
       }
     });

@@ -157,8 +157,11 @@ class AnalysisPlan:
         # furthest strided write against it)
         cap = out.untyped_storage().nbytes() // out.element_size() - out.storage_offset()
         n_out = c_int64(0)
+        # (a single series' stride(0) is arbitrary in torch; the C ABI checks the pol stride
+        # against n_dat whatever n_pol is)
+        in_ps = x.stride(0) if x.shape[0] > 1 else n_dat
         _lib.check(self._lib.pfb_filterbank_execute_strided(
-            self._h, c_void_p(x.data_ptr()), x.stride(0), n_dat, c_void_p(out.data_ptr()),
+            self._h, c_void_p(x.data_ptr()), in_ps, n_dat, c_void_p(out.data_ptr()),
             int(out_pol_stride), int(row_stride), int(chan_stride), int(sel[0]), int(sel[1]),
             int(sel[2]), int(cap), byref(n_out), _stream_of(x, self)))
         return int(n_out.value)

@@ -484,8 +484,8 @@ def test_c3_parameters_match_oracle(gpu):
     """BASELINE configs[2] parameters exactly (SKA-Mid padded, 4096 ch, 8/7, 100 353
     two-stage taps, Nf 512, Ov 128, tukey, deripple) at a reduced length (2^22 samples:
     1170 channelised rows, 3 synthesis blocks) through the production round trip —
-    fir_window_kernel<PADDED> writing the stage-1 rows, row_fft_kernel<4096>,
-    synth_block_kernel<512,448> — compared with orc.polyphase_analysis_padded ->
+    fir_lds_kernel writing the stage-1 rows, row_fft4096_pair_kernel,
+    synth_wave512_kernel — compared with orc.polyphase_analysis_padded ->
     orc.polyphase_synthesis (polyphase_analysis_padded.m:106-156,
     polyphase_synthesis.m:163-316): channelised product at unit amplitude (RMS), the
     synthesised series raw."""
