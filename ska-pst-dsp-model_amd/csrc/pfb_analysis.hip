@@ -132,6 +132,8 @@ __global__ __launch_bounds__(NT) void analysis_fused_kernel(AnalysisArgs a) {
   //    Bunton: v[(n + r) mod N] = u[n], r = (M k) mod N               (polyphase_analysis.m:102-105)
   //    padded: z[(n - idx) mod N] = y[n], idx barrel index             (polyphase_analysis_padded.m:132-144)
   LdsRows rows(smem, S_::RS);
+  // (padded: the barrel index counts rows modulo nu; one 64-bit remainder per thread)
+  [[maybe_unused]] const int bri0 = VARIANT == kPadded ? (int)((k0 + kk0) % a.nu) : 0;
 #pragma unroll
   for (int e = 0; e < S_::KPT; ++e) {
     const int k = kk0 + e * S_::KSTEP;
@@ -141,8 +143,11 @@ __global__ __launch_bounds__(NT) void analysis_fused_kernel(AnalysisArgs a) {
       const int r = (int)((kg * M) % N);
       pos = (n + r) % N;
     } else {
-      // idx = ((nu - (kg mod nu)) (N - M)) mod N = (M kg) mod N, since nu M = de N
-      const int idx = (int)((kg * M) & (N - 1));
+      // idx = ((nu - b)(N - M)) mod N with b = kg mod nu, 0 for b = 0.  This equals
+      // (M kg) mod N only where nu M = de N; M = floor(N de / nu) leaves a remainder for
+      // factors such as 5/3 at N = 16 (M = 9), as fir_generic_kernel already allows for.
+      const int b = (bri0 + e * S_::KSTEP) % a.nu;
+      const int idx = (b == 0) ? 0 : ((a.nu - b) * (N - M)) & (N - 1);
       pos = (n - idx + N) & (N - 1);
     }
     rows.store(k, pos, u[e]);

@@ -123,7 +123,7 @@ def test_analysis_many_taps_fused(gpu, N, os_, ppc):
     (1024, "4/3", 24, "bunton"),   # PW 25
     (512, "8/7", 19, "padded"),    # PW 25 (P 20)
     (512, "8/7", 28, "bunton"),    # PW 32 (P 29)
-    (512, "32/27", 12, "padded"),  # DE 27
+    (512, "32/27", 12, "padded"),  # fir_generic_kernel: P 13 < DE 27, no window instance
     (768, "8/7", 12, "bunton"),    # no row-FFT size for 768 -> rejected at plan time
 ])
 def test_analysis_generic_path(gpu, N, os_, ppc, variant):
