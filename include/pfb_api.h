@@ -136,8 +136,8 @@ pfb_status pfb_filterbank_reset(pfb_analysis_plan* plan);
  * FilterBank.m:93-104 over the carried + new samples); -1 on a null plan. */
 int64_t pfb_filterbank_output_rows(const pfb_analysis_plan* plan, int64_t n_in);
 
-/* The same stream call writing the channelised product strided (device buffers only,
- * streaming Bunton kernel: N = 256): bin c of row k of polarisation p goes to
+/* The same stream call writing the channelised product strided (device buffers only):
+ * bin c of row k of polarisation p goes to
  * out[p * out_pol_stride + k * row_stride + j * chan_stride], j = c, or with sel_n > 0
  * the cascade's channel chomp j = c < sel_split ? c : c - sel_shift (bins in
  * [sel_split, sel_split + sel_shift) and j >= sel_n dropped).  Serves the two-stage
@@ -145,10 +145,31 @@ int64_t pfb_filterbank_output_rows(const pfb_analysis_plan* plan, int64_t n_in);
  * chan_stride = series length) is the per-channel input of stage 2 with no corner turn;
  * stage 2 written with row_stride nch1*nch2, out_pol_stride nch2 and the chomp
  * (sel_split nch2/2-1, sel_shift = dropped bins) is the assembled output of
- * TwoStageFilterBank.m:102-105 with no gather.  PFB_ERR_UNSUPPORTED for other kernels.
- * out_capacity is the number of pfb_cf32 elements available from `out`: a call whose
- * furthest written element ((n_pol-1) out_pol_stride + (rows-1) row_stride + (j_max)
- * chan_stride) lies beyond it fails with PFB_ERR_BUFFER_TOO_SMALL and writes nothing. */
+ * TwoStageFilterBank.m:102-105 with no gather.
+ * Plans that take it: PFB_ANALYSIS_BUNTON on the streaming kernel (N = 256), and every
+ * PFB_ANALYSIS_PADDED plan pfb_filterbank_execute accepts (the fused kernels, N <= 256 with
+ * <= 32 tap phases, and the FIR + row-FFT path: N > 256, or more phases).
+ * PFB_ERR_UNSUPPORTED for other Bunton plans and for PFB_ANALYSIS_LOWCBF.
+ * Padded plans: the call computes K = floor((carried + n_in) / M) rows, FIR row kg becomes
+ * output row k = (kg - sds) mod K (polyphase_analysis_padded.m:156), and the *n_out = T_out
+ * = K - K mod os_nu rows k < T_out are stored through the layout.  Rows [T_out, K) are
+ * dropped at the store: unlike pfb_filterbank_execute there are no scratch rows in the
+ * caller's buffer and no staging copy — exactly the mapped elements are written.  The
+ * values are those of pfb_filterbank_execute, bit for bit, and the carry is the same
+ * (FilterBank.m:119-126).  Range limiting: a shifted row lands anywhere in [0, T_out) of
+ * its pol, so these kernels use guarded plain stores with 64-bit addresses (not a buffer
+ * descriptor): each store is predicated on k < T_out and a kept bin, and the only extent
+ * limit is that row_stride and chan_stride fit in 31 bits (else PFB_ERR_UNSUPPORTED).  The
+ * 4096-point row FFT stores channel-major output as 16-byte row pairs when `out` is 16-byte
+ * aligned and out_pol_stride and chan_stride are even, else as 8-byte elements.  (The
+ * Bunton streaming kernel range-limits each 16-row step with a buffer descriptor, whose
+ * extent 64 row_stride + j_max chan_stride must fit 2^31 bytes, else PFB_ERR_UNSUPPORTED.)
+ * Checks, all before any launch or change of the stream state: a bad layout (a stride
+ * <= 0, a negative sel_*, sel_split + sel_shift or sel_n beyond the channels) or
+ * in_pol_stride < n_in is PFB_ERR_INVALID_ARG; out_capacity is the number of pfb_cf32
+ * elements available from `out`: a call whose furthest written element ((n_pol-1)
+ * out_pol_stride + (rows-1) row_stride + (j_max) chan_stride) lies beyond it fails with
+ * PFB_ERR_BUFFER_TOO_SMALL and writes nothing. */
 pfb_status pfb_filterbank_execute_strided(pfb_analysis_plan* plan, const pfb_cf32* in,
                                           int64_t in_pol_stride, int64_t n_in, pfb_cf32* out,
                                           int64_t out_pol_stride, int64_t row_stride,

@@ -47,6 +47,11 @@ def main():
     ap.add_argument("--skip-mid", action="store_true")
     ap.add_argument("--only-mid", action="store_true")
     ap.add_argument("--only-twostage", action="store_true")
+    ap.add_argument("--padded-cascade", default="default",
+                    choices=["default", "strided", "no-stage1", "no-stage2", "gather"],
+                    help="the SKA-Mid padded cascade's stores: the library default; both stages strided; "
+                         "stage 1 through the corner turn (channel-major off); stage 2 through the gather "
+                         "(chomp off); or both off (TwoStageFilterBank.strided_stages)")
     ap.add_argument("--inflight", type=int, default=1, help="C3 units in flight (plan pairs/streams)")
     ap.add_argument("--graph", type=int, default=1, help="with --pipeline: capture the steps as one graph")
     ap.add_argument("--pipeline", type=int, default=0,
@@ -70,7 +75,7 @@ def main():
         return mid(torch, pfb, noise, dev, reps=args.reps, inflight=args.inflight, pipeline=bool(args.pipeline),
                    graph=bool(args.graph))
     if args.only_twostage:
-        return twostage(torch, pfb, noise, args.reps)
+        return twostage(torch, pfb, noise, args.reps, args.padded_cascade)
     # ---- C2' (4/3) round trip
     taps43 = pfb.design_PFB_FIR_filter(256, "4/3", 12)
     n = 1 << 24
@@ -123,7 +128,7 @@ def main():
         mid(torch, pfb, noise, dev)
 
 
-def twostage(torch, pfb, noise, reps):
+def twostage(torch, pfb, noise, reps, padded_cascade="default"):
     taps87 = pfb.design_PFB_FIR_filter(256, "8/7", 12)
     cfg = dict(analysis_function="polyphase_analysis", filt_coeff=taps87, channels=256,
                os_factor="8/7")
@@ -155,11 +160,16 @@ def twostage(torch, pfb, noise, reps):
     xm = noise(1, 1, nm)
     tm = pfb.TwoStageFilterBank(pcfg(taps1, 4096)).set_stage2_config(pcfg(taps2, 16))
     tm.critical = 1
+    stages = {"strided": [True, True], "no-stage1": [False, True], "no-stage2": [True, False],
+              "gather": [False, False]}.get(padded_cascade)
+    if stages is not None:
+        tm.strided_stages = stages
     tm.execute(xm)
     ms = timeit(torch, lambda: tm.execute(xm), reps)
     emit("TwoStageFilterBank SKA-Mid 4096x16 padded (stream call)", ms, 16 * (1 + 8 / 7) * nm,
          msamples_per_s=round(nm / ms / 1e3, 1),
-         note="both stages polyphase_analysis_padded; bytes: the two analyses' input+output")
+         note="both stages polyphase_analysis_padded; bytes: the two analyses' input+output",
+         **({} if stages is None else {"padded_cascade": padded_cascade}))
     del xm, tm
 
 

@@ -65,7 +65,10 @@ __device__ __forceinline__ void stage_span(float2* smem, const float2* __restric
 }
 
 // PMAX = compile-time tap phases; EXACT means P == PMAX (no clamping needed).
-template <int N, int PMAX, int VARIANT, int TDIV, bool EXACT>
+// STRIDED (padded variant, a.out_rs > 0): the last FFT pass stores through
+// AnalysisStridedStore — shifted row t at t * out_rs + j(c) * out_cs, rows t >= a.out_keep
+// and chomped bins dropped — instead of AnalysisStore's [t][c].
+template <int N, int PMAX, int VARIANT, int TDIV, bool EXACT, bool STRIDED = false>
 __global__ __launch_bounds__(NT) void analysis_fused_kernel(AnalysisArgs a) {
   static_assert(NT % N == 0, "fused analysis needs N | 256");
   using S_ = AnaShape<N, PMAX, TDIV>;
@@ -155,9 +158,16 @@ __global__ __launch_bounds__(NT) void analysis_fused_kernel(AnalysisArgs a) {
   __syncthreads();
 
   // 5. N-point DFT of every row; Bunton N*fft (forward), padded N^2*ifft (inverse dir.)
-  AnalysisStore st{a.out + pol * a.out_pol_stride, a.K, a.K_total, k0, N, a.sds, VARIANT == kPadded,
-                   (float)N};
-  block_fft<N, (VARIANT == kBunton) ? -1 : +1, T, NT>(rows, st, rows, smem + T * S_::RS, tid);
+  if constexpr (STRIDED) {
+    static_assert(VARIANT == kPadded, "strided store of the fused kernel: padded variant");
+    AnalysisStridedStore st{a.out + pol * a.out_pol_stride, a.K, a.K_total, k0, a.sds, (float)N,
+                            StridedOut{a.out_keep, a.out_rs, a.out_cs, a.sel_split, a.sel_shift, a.sel_n}};
+    block_fft<N, +1, T, NT>(rows, st, rows, smem + T * S_::RS, tid);
+  } else {
+    AnalysisStore st{a.out + pol * a.out_pol_stride, a.K, a.K_total, k0, N, a.sds, VARIANT == kPadded,
+                     (float)N};
+    block_fft<N, (VARIANT == kBunton) ? -1 : +1, T, NT>(rows, st, rows, smem + T * S_::RS, tid);
+  }
 }
 
 // ----------------------------------------------------------------------- streaming
@@ -658,10 +668,23 @@ static hipError_t launch_fused(const AnalysisArgs& a, hipStream_t s) {
   const size_t span = (size_t)a.M * (S_::T - 1) + (size_t)a.P * N;
   const size_t rows = (size_t)S_::T * S_::RS + tw_slots(N);  // FFT rows + twiddle table
   const size_t bytes = ((span + 1 > rows) ? span + 1 : rows) * sizeof(float2);
+  dim3 grid((unsigned)((a.K - a.row0 + S_::T - 1) / S_::T), (unsigned)a.n_pol);
+  if (a.out_rs > 0) {
+    // strided product (padded plans; the Bunton ones take the streaming kernel or none): one
+    // launch over all the call's rows, the shift being modulo K_total
+    if constexpr (VARIANT == kPadded) {
+      if (a.row0 != 0 || a.K != a.K_total || a.out_cs <= 0 || a.out_keep > a.K_total) return hipErrorInvalidValue;
+      auto kern = analysis_fused_kernel<N, PMAX, VARIANT, TDIV, EXACT, true>;
+      hipError_t e = set_lds(kern, bytes);
+      if (e != hipSuccess) return e;
+      return launch_kernel(kern, grid, dim3(NT), bytes, s, a);
+    } else {
+      return hipErrorInvalidValue;
+    }
+  }
   auto kern = analysis_fused_kernel<N, PMAX, VARIANT, TDIV, EXACT>;
   hipError_t e = set_lds(kern, bytes);
   if (e != hipSuccess) return e;
-  dim3 grid((unsigned)((a.K - a.row0 + S_::T - 1) / S_::T), (unsigned)a.n_pol);
   return launch_kernel(kern, grid, dim3(NT), bytes, s, a);
 }
 
@@ -848,6 +871,10 @@ hipError_t launch_analysis(const AnalysisArgs& a, hipStream_t s) {
   }
   if (!a.scratch && !a.z) return hipErrorInvalidValue;
   if (a.z_stage != 0 && !a.z) return hipErrorInvalidValue;
+  // strided product: padded plans, one launch over all the call's rows, scratch path
+  if (a.out_rs > 0 && (a.variant != kPadded || a.z || a.row0 != 0 || a.K != a.K_total || a.out_cs <= 0 ||
+                       a.out_keep > a.K_total))
+    return hipErrorInvalidValue;
   // generic: FIR into scratch, then row FFT (with the padded circular time shift)
   const int64_t rows = a.K - a.row0;
   const int64_t total = rows * a.N;
@@ -881,6 +908,14 @@ hipError_t launch_analysis(const AnalysisArgs& a, hipStream_t s) {
   }
   RowFftArgs r{a.scratch, rows * a.N, a.out, a.out_pol_stride, rows, nullptr, nullptr, a.twN,
                (float)a.N, a.sds, a.variant == kPadded, a.row0, a.K_total};
+  if (a.out_rs > 0) {
+    r.out_rs = a.out_rs;
+    r.out_cs = a.out_cs;
+    r.sel_split = a.sel_split;
+    r.sel_shift = a.sel_shift;
+    r.sel_n = a.sel_n;
+    r.out_keep = a.out_keep;
+  }
   if (a.variant == kBunton) return dispatch_row_fft<-1>(a.N, r, a.n_pol, s);
   return dispatch_row_fft<+1>(a.N, r, a.n_pol, s);
 }

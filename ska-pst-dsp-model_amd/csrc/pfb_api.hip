@@ -240,11 +240,13 @@ struct pfb_analysis_plan {
 // variant's circular shift is modulo K_total).  `in`/`out` are the call's bases.
 // z (round trip only): also emit the synthesis stage-1 rows of rows >= z_row0 into
 // z[pol][k - z_row0][t0] (AnalysisArgs::z).
-// Strided channelised output of the streaming analysis kernel (AnalysisArgs::out_rs):
-// pfb_filterbank_execute_strided
+// Strided channelised output (AnalysisArgs::out_rs): pfb_filterbank_execute_strided.
+// keep: the rows the call returns (T_out; a padded plan computes K >= T_out rows and stores
+// only the shifted rows below it, AnalysisArgs::out_keep)
 struct OutLayout {
   int64_t rs, cs;
   int32_t split, shift, nsel;
+  int64_t keep;
 };
 
 static pfb::AnalysisArgs analysis_args(const pfb_analysis_plan* p, const float2* in, int64_t in_ps, int64_t n_dat,
@@ -352,6 +354,7 @@ static pfb::AnalysisArgs analysis_args(const pfb_analysis_plan* p, const float2*
     a.sel_split = lay->split;
     a.sel_shift = lay->shift;
     a.sel_n = lay->nsel;
+    a.out_keep = lay->keep;
   }
   return a;
 }
@@ -617,15 +620,27 @@ pfb_status pfb_filterbank_execute_strided(pfb_analysis_plan* p, const pfb_cf32* 
                                           int32_t sel_shift, int32_t sel_n, int64_t cap,
                                           int64_t* n_out, void* stream) {
   if (!p || (!in && n_in > 0) || !out) return fail(PFB_ERR_INVALID_ARG, "null argument");
-  if (p->variant != pfb::kBunton || !analysis_offset_ok(p) || p->lowcbf_pad)
-    return fail(PFB_ERR_UNSUPPORTED, "strided output needs the streaming Bunton analysis kernel");
+  // every padded plan (fused kernel or FIR + row FFT: guarded plain stores, StridedOut), and
+  // the Bunton plans of the streaming kernel; nothing is launched and no state changes below
+  // until filterbank_exec has made its own checks
+  const bool padded = p->variant == pfb::kPadded;
+  if (!padded && (p->variant != pfb::kBunton || !analysis_offset_ok(p) || p->lowcbf_pad))
+    return fail(PFB_ERR_UNSUPPORTED,
+                "strided output needs a padded plan or the streaming Bunton analysis kernel");
   if (row_stride <= 0 || chan_stride <= 0 || sel_n < 0 || sel_split < 0 || sel_shift < 0 ||
       (sel_n > 0 && sel_split + sel_shift > p->C) || sel_n > p->C)
     return fail(PFB_ERR_INVALID_ARG, "bad strided output layout");
-  // one 16-row step's extent must fit a 32-bit buffer descriptor (StridedRowStore)
   const int64_t jn = sel_n > 0 ? sel_n : p->C;
-  if ((64 * row_stride + jn * chan_stride + 1) * 8 > pfb::kRsrcMaxBytes)
+  if (padded) {
+    // the kernels hold the two strides as 32-bit ints and form 64-bit element offsets from
+    // them: no descriptor, no extent limit beyond that
+    if (row_stride > INT32_MAX || chan_stride > INT32_MAX)
+      return fail(PFB_ERR_UNSUPPORTED, "strided output: a stride exceeds 2^31 - 1 elements");
+    if (out_ps < 0) return fail(PFB_ERR_INVALID_ARG, "negative polarisation stride");
+  } else if ((64 * row_stride + jn * chan_stride + 1) * 8 > pfb::kRsrcMaxBytes) {
+    // one 16-row step's extent must fit a 32-bit buffer descriptor (StridedRowStore)
     return fail(PFB_ERR_UNSUPPORTED, "strided output extent exceeds a buffer descriptor");
+  }
   // out_capacity counts pfb_cf32 elements from `out`: the furthest element this call writes
   // must lie inside it (a wrong stride is rejected, not written past the buffer)
   const int64_t Kt = pfb_filterbank_output_rows(p, n_in);
@@ -637,7 +652,7 @@ pfb_status pfb_filterbank_execute_strided(pfb_analysis_plan* p, const pfb_cf32* 
                   "strided output: element %lld is written but out_capacity is %lld elements",
                   (long long)last, (long long)cap);
   }
-  const OutLayout lay{row_stride, chan_stride, sel_split, sel_shift, sel_n};
+  const OutLayout lay{row_stride, chan_stride, sel_split, sel_shift, sel_n, std::max<int64_t>(Kt, 0)};
   return filterbank_exec(p, in, in_ps, n_in, out, out_ps, std::max<int64_t>(Kt, 0), n_out, PFB_MEM_DEVICE,
                          stream, &lay);
 }
@@ -740,7 +755,11 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
     const int64_t K = analysis_K(p, total);
     const int64_t Kt = K - (K % p->nu);
     const int64_t input_idat = (Kt * p->N * p->de) / p->nu;
-    if (mem == PFB_MEM_DEVICE && B > 0 && !lay && !p->lowcbf_pad && p->fused && analysis_fused_carry_ok(p) &&
+    // (a layout — pfb_filterbank_execute_strided on a padded plan; the Bunton plans it admits
+    // take the streaming kernel above — goes straight to `out`: the launch stores the shifted
+    // rows below Kt through the layout and drops rows [Kt, K), so there are no scratch rows
+    // and no staging buffer)
+    if (mem == PFB_MEM_DEVICE && B > 0 && !p->lowcbf_pad && p->fused && analysis_fused_carry_ok(p) &&
         input_idat >= B && Kt > 0) {
       if (n_out) *n_out = Kt;
       if (Kt > cap) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld rows",
@@ -750,13 +769,13 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
       int64_t dps = out_ps;
       // (the scratch rows [Kt, Krun) need room in the pol's own stride too: pols packed
       // closer than Krun rows would have them land on the next pol's first rows)
-      if (Krun > cap || out_ps < Krun * p->C) {
+      if (!lay && (Krun > cap || out_ps < Krun * p->C)) {
         HIPCHK(p->stage_out.ensure((size_t)p->n_pol * Krun * p->C * sizeof(float2)));
         dst = p->stage_out.as<float2>();
         dps = Krun * p->C;
       }
       pfb_status st = analysis_run(p, (const float2*)in, in_ps, n_in, dst, dps, 0, Krun, K, s, nullptr, 0, 0, B,
-                                   nullptr, 0, p->carry.as<float2>());
+                                   lay, 0, p->carry.as<float2>());
       if (st != PFB_OK) return st;
       if (dst != (float2*)out)
         HIPCHK(copy_pols((float2*)out, out_ps, dst, dps, Kt * p->C, p->n_pol, hipMemcpyDeviceToDevice, s));
@@ -813,13 +832,15 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
       // each pol's stride (rows [Kt, K) are then scratch, pfb_filterbank_execute's contract),
       // else through a staging buffer and a copy
       // (round 6: the SKA-Mid cascade's stage 2 lost a 244-us copy per call)
-      if (Krun > cap || (!lay && out_ps < Krun * p->C)) {
+      // (a layout: `cap` is the Kt rows the strided entry point range-checked and out_ps is
+      // the layout's; the launch writes `out` directly — a padded plan's K rows run with the
+      // shifted rows [Kt, K) dropped at the store, AnalysisArgs::out_keep)
+      if (!lay && (Krun > cap || out_ps < Krun * p->C)) {
         HIPCHK(p->stage_out.ensure((size_t)p->n_pol * Krun * p->C * sizeof(float2)));
         dst = p->stage_out.as<float2>();
         dps = Krun * p->C;
       }
     }
-    if (lay && dst != (float2*)out) return fail(PFB_ERR_UNSUPPORTED, "strided output through a staging buffer");
     pfb_status st = analysis_run(p, w, wps, total, dst, dps, 0, Krun, K, s, nullptr, 0, 0, 0, lay);
     if (st != PFB_OK) return st;
     if (dst != (float2*)out) {

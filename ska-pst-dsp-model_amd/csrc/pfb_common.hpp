@@ -122,6 +122,56 @@ struct AnalysisStore {
   }
 };
 
+// Strided layout of the padded variant's channelised product (AnalysisArgs::out_rs > 0,
+// pfb_filterbank_execute_strided): bin c of output row t — the row AFTER the circular -sds
+// shift — lies at t * rs + j(c) * cs of its pol, with the cascade's chomp j(c) when nsel > 0
+// (TwoStageFilterBank.m:102-105).  Rows t >= keep (the nu-trim of FilterBank.m:93-104: the
+// shift spans all K computed rows, T_out of them are returned) and chomped bins have no
+// place in the caller's buffer: at() returns -1 and the store is skipped.  Guarded plain
+// stores, as AnalysisStore and RowStore: a shifted row lands anywhere in [0, keep) of its
+// pol, so no per-workgroup descriptor extent bounds it, and 64-bit addressing has no
+// extent limit (the host checks the furthest element against the capacity).
+struct StridedOut {
+  int64_t keep;
+  int rs, cs, split, shift, nsel;
+  __device__ __forceinline__ int64_t at(int64_t t, int c) const {
+    // (bitwise, not short-circuit: StridedRowStore's note)
+    int j = c;
+    bool ok = t < keep;
+    if (nsel > 0) {  // uniform
+      j = c < split ? c : c - shift;
+      ok = ok & ((c < split) | (c >= split + shift)) & (j < nsel);
+    }
+    return ok ? t * rs + (int64_t)j * cs : (int64_t)-1;
+  }
+  // channel-major (rs = 1: a cascade's stage-1 product, read by stage 2 next) at the default
+  // cache policy, assembled rows (nobody re-reads them) nontemporal — kAuxColMajor /
+  // kAuxStrided of the streaming kernel's strided stores
+  __device__ __forceinline__ void put(float2* out, int64_t i, float2 v) const {
+    if (i < 0) return;
+    if (rs == 1) st_nt<kAuxColMajor == 2>(out + i, v);
+    else st_nt<kAuxStrided == 2>(out + i, v);
+  }
+};
+
+// AnalysisStore's strided twin (analysis_fused_kernel, padded variant)
+struct AnalysisStridedStore {
+  static constexpr bool kIsLds = false;
+  float2* out;
+  int64_t K, Ktot, k0;  // as AnalysisStore (a strided launch covers all Ktot rows)
+  int sds;
+  float scale;
+  StridedOut lay;
+  __device__ __forceinline__ void store(int row, int c, float2 v) const {
+    const int64_t kg = k0 + row;
+    if (kg < K) {
+      int64_t t = kg - sds;  // polyphase_analysis_padded.m:156
+      while (t < 0) t += Ktot;
+      lay.put(out, lay.at(t, c), cscale(v, scale));
+    }
+  }
+};
+
 // Row store through a range-checked buffer descriptor: rows [lo, records / (8 N)) of
 // the descriptor's base are written, others dropped by the hardware (an out-of-range
 // offset) — no branch per store, so the wave's vmcnt count stays path-independent and
@@ -264,6 +314,26 @@ struct RowStore {
   }
 };
 
+// RowStore's strided twin (StridedOut): the generic path's row FFT of a padded plan writing
+// a strided product.  The launch covers the call's rows from row 0 (row_base = 0).
+struct RowStridedStore {
+  static constexpr bool kIsLds = false;
+  float2* out;
+  int64_t r0, n_rows;
+  int64_t sds;
+  float scale;
+  int64_t n_total;
+  StridedOut lay;
+  __device__ __forceinline__ void store(int row, int c, float2 v) const {
+    const int64_t r = r0 + row;
+    if (r < n_rows) {
+      int64_t t = r - sds;
+      while (t < 0) t += n_total;
+      lay.put(out, lay.at(t, c), cscale(v, scale));
+    }
+  }
+};
+
 // XCD-aware tile order: workgroups b and b+8 share an XCD (and its L2); give them
 // consecutive tiles so the halo of one tile is an L2 hit for its neighbour.
 // Bijective for any grid size (cdna_hip_programming.md, "XCD swizzle must be bijective").
@@ -292,6 +362,11 @@ struct RowFftArgs {
   int in_run = 0;    // input rows in 2-row runs per column (z_index), the SKA-Mid stage-1 rows
   int rev = 0;       // perm is the index reversal (N - i) mod N (the 4096-point pair kernel
                      // computes it instead of holding 16 column offsets per thread)
+  // strided product of a padded plan (AnalysisArgs::out_rs > 0; StridedOut): remap set,
+  // row_base 0, n_rows = n_total, no perm / gain / runs; out_keep = the rows kept (T_out)
+  int out_rs = 0, out_cs = 0;
+  int sel_split = 0, sel_shift = 0, sel_n = 0;
+  int64_t out_keep = 0;
 };
 
 template <int N>
@@ -300,15 +375,22 @@ struct RowShape {
   static constexpr int RS = lds_row(N);
 };
 
-template <int N, int DIR, bool PERM, bool GAIN>
+// STRIDED: the rows go out through RowStridedStore (a.out_rs > 0) instead of RowStore
+template <int N, int DIR, bool PERM, bool GAIN, bool STRIDED = false>
 __global__ __launch_bounds__(NT) void row_fft_kernel(RowFftArgs a) {
   constexpr int ROWS = RowShape<N>::ROWS;
   extern __shared__ __attribute__((aligned(16))) float2 smem[];
   const int pol = blockIdx.y;
   const int64_t r0 = (int64_t)blockIdx.x * ROWS;
   RowLoad<PERM, GAIN> ld{a.in + pol * a.in_pol_stride, r0, a.n_rows - 1, N, a.perm, a.cgain, a.in_run};
-  RowStore st{a.out + pol * a.out_pol_stride, r0, a.n_rows, N, a.sds, a.remap, a.scale,
-              a.row_base, a.n_total, a.zs, a.nt};
+  auto st = [&] {
+    if constexpr (STRIDED)
+      return RowStridedStore{a.out + pol * a.out_pol_stride, r0, a.n_rows, a.sds, a.scale, a.n_total,
+                             StridedOut{a.out_keep, a.out_rs, a.out_cs, a.sel_split, a.sel_shift, a.sel_n}};
+    else
+      return RowStore{a.out + pol * a.out_pol_stride, r0, a.n_rows, N, a.sds, a.remap, a.scale,
+                      a.row_base, a.n_total, a.zs, a.nt};
+  }();
   LdsRows rows(smem, RowShape<N>::RS);
   // twiddle table -> LDS behind the rows (ordered before pass 2 by its barrier)
   float2* tw = smem + ROWS * RowShape<N>::RS;

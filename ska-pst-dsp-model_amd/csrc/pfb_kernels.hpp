@@ -69,10 +69,16 @@ struct AnalysisArgs {
   const float2* pre;
   int64_t pre_pol_stride;
   float lcbf_scale;  // LowCBF streaming path: output scale (2^12)
-  // Strided channelised output (streaming kernel only, out_rs > 0): bin c of row k goes to
+  // Strided channelised output (out_rs > 0): bin c of row k goes to
   // out[pol][k * out_rs + j * out_cs] with j = c (sel_n = 0) or the two-stage chomp
   // j = c < sel_split ? c : c - sel_shift, kept when c < sel_split or c >= sel_split +
-  // sel_shift, and j < sel_n (TwoStageFilterBank.m:102-105); out_rs = 0: [pol][k][c]
+  // sel_shift, and j < sel_n (TwoStageFilterBank.m:102-105); out_rs = 0: [pol][k][c].
+  // Taken by the streaming kernel (Bunton, N = 256; rows [row0, K) through per-step
+  // descriptors, StridedRowStore) and by every padded plan: the fused kernel
+  // (AnalysisStridedStore) and the generic path's row FFTs (RowStridedStore, the 4096-point
+  // pair kernel's OST mode).  Padded: k is the row after the circular -sds shift, the launch
+  // covers all K_total rows (row0 = 0, K = K_total), and only shifted rows k < out_keep are
+  // stored — guarded plain stores, no scratch rows in `out`
   int out_rs, out_cs;
   int sel_split, sel_shift, sel_n;
   // z in a grouped layout (streaming kernel, round trip into synth_wave_kernel): zblk = ZB
@@ -92,6 +98,9 @@ struct AnalysisArgs {
   // workgroup -> step range order: 0 XCD-aware (xcd_tile), 1 linear (blockIdx.x: the
   // dispatcher's order is the rows' order, so the chip's loads in flight stay in one window)
   int linear = 0;
+  // padded plans with out_rs > 0: the rows kept of the K_total computed (the stream object's
+  // nu-trimmed T_out, FilterBank.m:93-104); shifted rows [out_keep, K_total) are not stored
+  int64_t out_keep = 0;
 };
 // SKA-Low CBF PST filterbank through the streaming analysis kernel (pfb_analysis.hip)
 hipError_t launch_lowcbf_stream(const AnalysisArgs& a, hipStream_t s);

@@ -300,6 +300,84 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3))) void ro
   }
 }
 
+// The pair kernel for a padded plan's strided product (RowFftArgs::out_rs > 0, StridedOut;
+// pfb_filterbank_execute_strided): rows paired by OUTPUT row.  The workgroup of pair g
+// (g = xcd_tile(blockIdx.x), see below) makes output rows
+// t = 2g and 2g + 1 from the FIR rows (t + sds) mod K — consecutive except at the single
+// wrap, and each read through its own one-row descriptor (lane offset tid * 8, the
+// register's r * 2048 as the scalar offset: inside the row by construction) — so a pair
+// never starts odd when sds is odd and never straddles the wrap.  Only t < out_keep is made
+// (the nu-trim: rows [T_out, K) are neither transformed nor stored); the last pair of an odd
+// out_keep has no row B: its loads re-read row A and are never transformed (the !RUN rule of
+// row_fft4096_pair_kernel).  Channel-major output (out_rs = 1, a cascade's stage-1 product)
+// holds both rows' results and stores bin c of the pair as one 16-B element at c * out_cs +
+// 2g, as OZS does for its runs; that needs the base 16-B aligned and out_cs, out_pol_stride
+// even (uniform test, else two 8-B stores).  Any other layout: two 8-B stores per bin,
+// coalesced across lanes when out_cs = 1.  Guarded plain stores (StridedOut).  Same passes
+// and tables as the other 4096-point kernels: bit-identical values.
+template <int DIR>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3))) void row_fft4096_pair_strided_kernel(
+    RowFftArgs a) {
+  constexpr int N = 4096;
+  extern __shared__ __attribute__((aligned(16))) float2 smem[];
+  const int pol = blockIdx.y;
+  // XCD-aware pair order (xcd_tile): consecutive pairs are consecutive workgroups of ONE XCD,
+  // so the eight 16-B pieces of a channel-major 128-B line (16 rows of one channel) meet in
+  // that XCD's L2 and leave it as one line.  In blockIdx order they come from eight L2s as
+  // partial lines: the SKA-Mid cascade 1.84-1.90 ms against 1.50-1.53 with this order, and
+  // nontemporal pair stores 2.8-2.9 (profiles/twostage_strided_padded_ab.jsonl)
+  const int64_t t0 = 2 * (int64_t)xcd_tile(blockIdx.x, gridDim.x);
+  if (t0 >= a.out_keep) return;  // uniform per workgroup
+  const bool has_b = t0 + 1 < a.out_keep;
+  const int tid = threadIdx.x;
+  float2* row = smem;
+  float2* t2 = smem + kR4kRow;
+  float2* t3 = t2 + kR4kTw2;
+  for (int e = tid; e < kR4kTw3; e += NT) {
+    const int pp = e >> 8, k = e & 255;
+    t3[e] = a.tw[(k << pp) & (N - 1)];
+    if (e < kR4kTw2) t2[e] = a.tw[((e & 15) << ((e >> 4) + 4)) & (N - 1)];
+  }
+  const float2* in = a.in + pol * a.in_pol_stride;
+  float2* out = a.out + pol * a.out_pol_stride;
+  // FIR row of output row t: (t + sds) mod K (polyphase_analysis_padded.m:156 read backwards);
+  // t < out_keep <= K and sh < K: one wrap
+  const int64_t sh = a.sds % a.n_total;
+  int64_t ra = t0 + sh, rb = has_b ? t0 + 1 + sh : t0 + sh;
+  if (ra >= a.n_total) ra -= a.n_total;
+  if (rb >= a.n_total) rb -= a.n_total;
+  const __amdgpu_buffer_rsrc_t rsa = make_rsrc_u(in + ra * N, (uint32_t)(N * 8));
+  const __amdgpu_buffer_rsrc_t rsb = make_rsrc_u(in + rb * N, (uint32_t)(N * 8));
+  const uint32_t lane_off = (uint32_t)tid * 8u;
+  float2 v[16], h[16];
+  static_for<0, 16>([&](auto rv) {
+    constexpr int r = decltype(rv)::value;
+    v[r] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rsa, lane_off, r * 2048, kNtlRow ? 2 : 0));
+    h[r] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rsb, lane_off, r * 2048, kNtlRow ? 2 : 0));
+  });
+  r4k_fft<DIR>(v, row, t2, t3, tid);
+  if (has_b) r4k_fft<DIR>(h, row, t2, t3, tid);  // (uniform)
+  const StridedOut lay{a.out_keep, a.out_rs, a.out_cs, a.sel_split, a.sel_shift, a.sel_n};
+  const bool wide = has_b && a.out_rs == 1 && ((a.out_cs | a.out_pol_stride) & 1) == 0 &&
+                    (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
+  if (wide) {
+    static_for<0, 16>([&](auto rv) {
+      constexpr int r = decltype(rv)::value;
+      const int64_t i = lay.at(t0, tid + 256 * r);  // rows 2g and 2g + 1 < out_keep: same bins kept
+      if (i >= 0) {
+        const float2 x0 = cscale(v[r], a.scale), x1 = cscale(h[r], a.scale);
+        *reinterpret_cast<v4f*>(out + i) = v4f{x0.x, x0.y, x1.x, x1.y};
+      }
+    });
+  } else {
+    static_for<0, 16>([&](auto rv) {
+      constexpr int r = decltype(rv)::value;
+      lay.put(out, lay.at(t0, tid + 256 * r), cscale(v[r], a.scale));
+      if (has_b) lay.put(out, lay.at(t0 + 1, tid + 256 * r), cscale(h[r], a.scale));
+    });
+  }
+}
+
 template <int DIR, bool PERM, bool GAIN>
 static hipError_t launch_row_fft4096(const RowFftArgs& r, int n_pol, hipStream_t s, int per_cu) {
   auto kern = row_fft4096_kernel<DIR, PERM, GAIN>;
@@ -334,6 +412,32 @@ static hipError_t launch_row_fft4096_pair(const RowFftArgs& r, int n_pol, hipStr
 template <int N, int DIR, bool PERM, bool GAIN>
 static hipError_t launch_row_fft_t(const RowFftArgs& r, int n_pol, hipStream_t s) {
   constexpr int ROWS = RowShape<N>::ROWS;
+  if (r.out_rs > 0) {
+    // strided product of a padded plan (launch_analysis' generic path): the whole call's
+    // rows in one launch, plain [row][N] input, inverse-direction FFT, no perm / gain
+    if constexpr (DIR > 0 && !PERM && !GAIN && (N & (N - 1)) == 0) {
+      if (!r.remap || r.row_base != 0 || r.n_rows != r.n_total || r.zs != 0 || r.in_run || r.out_cs <= 0 ||
+          r.out_keep <= 0 || r.out_keep > r.n_total)
+        return hipErrorInvalidValue;
+      if constexpr (N == 4096) {
+        auto kern = row_fft4096_pair_strided_kernel<DIR>;
+        hipError_t e = set_lds(kern, kR4kLds);
+        if (e != hipSuccess) return e;
+        const int64_t wgs = (r.out_keep + 1) / 2;  // one pair of output rows per workgroup
+        if (wgs > INT32_MAX) return hipErrorInvalidValue;
+        return launch_kernel(kern, dim3((unsigned)wgs, (unsigned)n_pol), dim3(NT), kR4kLds, s, r);
+      } else {
+        const size_t bytes = ((size_t)ROWS * RowShape<N>::RS + tw_slots(N)) * sizeof(float2);
+        auto kern = row_fft_kernel<N, DIR, false, false, true>;
+        hipError_t e = set_lds(kern, bytes);
+        if (e != hipSuccess) return e;
+        dim3 grid((unsigned)((r.n_rows + ROWS - 1) / ROWS), (unsigned)n_pol);
+        return launch_kernel(kern, grid, dim3(NT), bytes, s, r);
+      }
+    } else {
+      return hipErrorInvalidValue;
+    }
+  }
   if constexpr (N == 4096) {
     // persistent workgroups (row_fft_persist_kernel) once there are several rows per
     // resident workgroup; PFB_ROWFFT_PERSIST=0: one workgroup per row (A/B)

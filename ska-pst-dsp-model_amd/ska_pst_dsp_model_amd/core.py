@@ -149,7 +149,12 @@ class AnalysisPlan:
         sample stride) writing bin c of row k of pol p to
         ``out``'s storage at p * out_pol_stride + k * row_stride + j * chan_stride
         (``pfb_filterbank_execute_strided``; sel = (split, shift, n) is the cascade's
-        channel chomp).  Returns the number of rows written."""
+        channel chomp).  Returns the number of rows written.  Plans: ``polyphase_analysis``
+        on the streaming kernel (N = 256) and every ``polyphase_analysis_padded`` plan;
+        others raise ``PfbError`` with ``PFB_ERR_UNSUPPORTED``.  A padded plan stores exactly
+        the returned T_out rows: the rows [T_out, K) of its circular shift are dropped at
+        the store (no scratch rows in ``out``, no staging copy), with guarded plain stores,
+        so the layout's extent is limited only by ``out``'s capacity."""
         if x.shape[0] != self.n_pol or x.stride(1) != 1:
             raise ValueError("execute_strided: (n_pol, n_dat) series with unit sample stride")
         n_dat = int(x.shape[1])

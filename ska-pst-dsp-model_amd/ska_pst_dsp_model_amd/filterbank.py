@@ -214,8 +214,17 @@ class TwoStageFilterBank(Channelizer):
     writes its product channel-major, so pol 1's channels are the stage-2 series as
     they lie, and the batched stage 2 writes the assembled output with the oversampled
     channels chomped out (:102-105) straight from its FFT
-    (``pfb_filterbank_execute_strided``, streaming kernel shapes); other shapes take a
-    corner turn (``pfb_corner_turn``) and a gather (``pfb_gather_channels``)."""
+    (``pfb_filterbank_execute_strided``: the streaming-kernel shapes of
+    ``polyphase_analysis`` and every ``polyphase_analysis_padded`` plan, whose strided call
+    also drops the rows [T_out, K) of the circular shift at the store).  A stage that does
+    not store strided takes a corner turn (``pfb_corner_turn``, stage 1) or a gather
+    (``pfb_gather_channels``, stage 2): stages whose plan has no strided store, all of them
+    with ``strided = False``, and the stages ``_STRIDED_DEFAULT`` leaves on that path.  Every
+    combination computes the same values, bit for bit."""
+
+    # (stage 1 channel-major, stage 2 assembled + chomped) by default, per analysis function:
+    # the measured-faster path of each stage (DESIGN.md §6, profiles/twostage_strided_padded_ab.jsonl)
+    _STRIDED_DEFAULT = {"padded": (True, True), "other": (True, True)}
 
     def __init__(self, config, device: int = 0):
         self.stage1 = FilterBank(config, device=device)
@@ -231,6 +240,9 @@ class TwoStageFilterBank(Channelizer):
         # both stages through pfb_filterbank_execute_strided where the kernels allow it
         # (no corner turn, no gather); False: the corner-turn / gather path
         self.strided = True
+        # A/B runs: (stage 1, stage 2) True / False forces that stage's strided store on or
+        # off; None: the default (_stage_strided)
+        self.strided_stages = [None, None]
 
     def set_stage2_config(self, config):
         self.config2 = config
@@ -248,12 +260,29 @@ class TwoStageFilterBank(Channelizer):
             self.build()
         view = self._execute_strided(x) if self.strided else None
         if view is None:
-            _, out1 = self.stage1.execute(x)      # (n_pol, nch1, T1) view
-            nch1 = 1 if self.single == 1 else self.stage1.n_chan
-            # per-channel series of pol 1: (T1, nch1) rows -> (nch1, T1)
-            rows = out1[0].transpose(0, 1)[:, :nch1]  # (T1, nch1) view of the engine buffer
-            view = self._stage2(layout.corner_turn(rows), nch1)
+            series, nch1 = self._stage1_turned(x)
+            view = self._stage2(series, nch1)
         return self, (_to_host(view) if host else view)
+
+    def _stage1_turned(self, x):
+        """Stage 1 through the contiguous call, then the corner turn: the (nch1, T1)
+        per-channel series of pol 1."""
+        _, out1 = self.stage1.execute(x)      # (n_pol, nch1, T1) view
+        nch1 = 1 if self.single == 1 else self.stage1.n_chan
+        # per-channel series of pol 1: (T1, nch1) rows -> (nch1, T1)
+        rows = out1[0].transpose(0, 1)[:, :nch1]  # (T1, nch1) view of the engine buffer
+        return layout.corner_turn(rows), nch1
+
+    def _stage_strided(self, stage: int) -> bool:
+        """Does ``stage`` (1 or 2) store strided?  ``strided_stages[stage - 1]`` when it is
+        set (A/B runs), else the measured default for the stage's analysis function
+        (``_STRIDED_DEFAULT``)."""
+        forced = self.strided_stages[stage - 1]
+        if forced is not None:
+            return bool(forced)
+        fb = self.stage1 if stage == 1 else self.stage2
+        padded = fb.pfb_analysis in ("polyphase_analysis_padded", "padded")
+        return self._STRIDED_DEFAULT["padded" if padded else "other"][stage - 1]
 
     def _chomp(self):
         """(nch2 kept per stage-2 bank, dropped-bin count) of :81-85,102-105."""
@@ -281,32 +310,44 @@ class TwoStageFilterBank(Channelizer):
         """Both stages through pfb_filterbank_execute_strided: stage 1 writes its product
         channel-major, so pol 1's channels are already the stage-2 series (no corner
         turn), and stage 2 writes the assembled, chomped output (no gather).  Same
-        kernels and arithmetic as the corner-turn / gather path (bit-identical).  None
-        when stage 1 cannot take this path (its plan state is then untouched); a stage 2
-        that cannot takes the gather path."""
+        kernels and arithmetic as the corner-turn / gather path (bit-identical).  Padded
+        stages: the strided call stores only the T_out rows it returns (the rows [T_out, K)
+        of the padded variant's circular shift are dropped at the store, not written as
+        scratch).  None when stage 1 cannot take this path (its plan state is then
+        untouched); a stage 2 that cannot takes the gather path.  A stage ``_stage_strided``
+        turns off takes its corner turn / gather while the other stays strided."""
         from ._lib import PFB_ERR_UNSUPPORTED, PfbError
         s1, s2 = self.stage1, self.stage2
         if s1.rndInput or s1.rndOutput or s2.rndInput or s2.rndOutput:
             return None
+        use1, use2 = self._stage_strided(1), self._stage_strided(2)
+        if not (use1 or use2):
+            return None
         import torch
-        p1 = s1._ensure_plan(_npol(x))
-        xs, _ = p1._prep_in(x)
-        T1 = p1.stream_rows(int(xs.shape[1]))
-        nch1_all = p1.out_chan
-        T1c = max(16, (T1 + 15) // 16 * 16)  # 128-B aligned channel runs
-        ser = torch.empty((p1.n_pol, nch1_all, T1c), dtype=torch.complex64, device=xs.device)
-        try:
-            T1 = p1.execute_strided(xs, ser, nch1_all * T1c, 1, T1c)
-        except PfbError as e:
-            if e.status == PFB_ERR_UNSUPPORTED:
-                return None
-            raise
-        nch1 = 1 if self.single == 1 else nch1_all
-        series = ser[0, :nch1, :T1]               # (nch1, T1), unit sample stride
+        if use1:
+            p1 = s1._ensure_plan(_npol(x))
+            xs, _ = p1._prep_in(x)
+            T1 = p1.stream_rows(int(xs.shape[1]))
+            nch1_all = p1.out_chan
+            T1c = max(16, (T1 + 15) // 16 * 16)  # 128-B aligned channel runs
+            ser = torch.empty((p1.n_pol, nch1_all, T1c), dtype=torch.complex64, device=xs.device)
+            try:
+                T1 = p1.execute_strided(xs, ser, nch1_all * T1c, 1, T1c)
+            except PfbError as e:
+                if e.status == PFB_ERR_UNSUPPORTED:
+                    return None
+                raise
+            nch1 = 1 if self.single == 1 else nch1_all
+            series = ser[0, :nch1, :T1]               # (nch1, T1), unit sample stride
+        else:
+            series, nch1 = self._stage1_turned(x)
+            T1 = int(series.shape[1])
+        if not use2:
+            return self._stage2(series, nch1)
         nch2, offset = self._chomp()
         p2 = s2._ensure_plan(nch1)
         T2 = p2.stream_rows(T1)
-        out = torch.empty((1, max(T2, 1), nch1 * nch2), dtype=torch.complex64, device=xs.device)
+        out = torch.empty((1, max(T2, 1), nch1 * nch2), dtype=torch.complex64, device=series.device)
         try:
             T2 = p2.execute_strided(series, out, nch2, nch1 * nch2, 1,
                                     (nch2 // 2 - 1, offset, nch2))
