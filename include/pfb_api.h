@@ -59,7 +59,14 @@ typedef enum pfb_analysis_variant {
   PFB_ANALYSIS_PADDED = 1, /* polyphase_analysis_padded.m */
   PFB_ANALYSIS_LOWCBF = 2  /* polyphase_analysis_lowcbf.m -> PSTFilterbank.m: the SKA-Low CBF
                               PST filterbank (n_chan 256, os 4/3, 3072 taps fixed); 216
-                              output channels; 1536 zeros pre-padded on the plan's first call */
+                              output channels; 1536 zeros pre-padded on the plan's first call.
+                              "First call" = the first pfb_analysis_execute /
+                              pfb_filterbank_execute that passes every argument check (it may
+                              return no rows, as the Matlab wrapper's first call may); a call
+                              rejected with an error status (null output, capacity, stride)
+                              leaves the padding pending and the length queries unchanged, so
+                              the corrected retry returns the rows a first call returns.
+                              pfb_filterbank_reset makes the padding due again. */
 } pfb_analysis_variant;
 
 typedef enum pfb_mem {

@@ -207,10 +207,18 @@ const char*& pfb::launched_kernel_name() { return g_launched; }
 pfb_status pfb_set_error(pfb_status s, const char* msg) { return fail(s, "%s", msg); }
 
 // ====================================================================== analysis plan
-// LowCBF: every call consumes the one-time pre-padding (polyphase_analysis_lowcbf.m:27-34)
+// LowCBF: a call that passed every argument check consumes the one-time pre-padding
+// (polyphase_analysis_lowcbf.m:27-34) when it returns — a successful call without output rows
+// too, as the Matlab wrapper does.  A rejected call (null output, capacity, stride) returns
+// before `accept()` and leaves the padding pending, so the corrected retry computes the same
+// rows a first call would have.  (The launch reads the flag: it is cleared on exit, not here.)
 struct PadConsume {
   bool* flag;
-  ~PadConsume() { *flag = false; }
+  bool accepted = false;
+  void accept() { accepted = true; }
+  ~PadConsume() {
+    if (accepted) *flag = false;
+  }
 };
 
 struct pfb_analysis_plan {
@@ -575,13 +583,17 @@ pfb_status pfb_analysis_execute(pfb_analysis_plan* p, const pfb_cf32* in, int64_
   const int64_t K = analysis_K(p, n_dat);
   PadConsume pad_once{&p->lowcbf_pad};
   if (n_out) *n_out = K;
-  if (K == 0) return PFB_OK;
+  if (K == 0) {
+    pad_once.accept();
+    return PFB_OK;
+  }
   if (!out) return fail(PFB_ERR_INVALID_ARG, "null output");
   if (cap < K) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld rows",
                            (long long)cap, (long long)K);
+  if (mem == PFB_MEM_DEVICE && (in_ps < n_dat || out_ps < K * p->C))
+    return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
+  pad_once.accept();
   if (mem == PFB_MEM_DEVICE) {
-    if (in_ps < n_dat || out_ps < K * p->C)
-      return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
     return analysis_run(p, (const float2*)in, in_ps, n_dat, (float2*)out, out_ps, 0, K, K, s);
   }
   // host staging (synchronous)
@@ -814,6 +826,7 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
   if (n_out) *n_out = Kt;
   if (Kt > cap) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld rows",
                             (long long)cap, (long long)Kt);
+  pad_once.accept();
   if (Kt > 0) {
     // rows are independent except for the padded variant's circular shift over all K
     // rows: the others compute just the Kt kept rows, straight into the caller's buffer

@@ -415,6 +415,86 @@ def test_filterbank_padded_generic_layout(gpu, layout):
     assert seen == ((4 + 7 + 2) if layout == "roomy" else 0)
 
 
+# ------------------------------------------------------------------- rejected LowCBF calls
+BUFFER_TOO_SMALL = 5
+LOWCBF_REJECTS = {
+    # name -> (capacity rows, out_pol_stride, null out) from the call's (K, C), expected status
+    "capacity-one-row-short": (lambda K, C: (K - 1, K * C, False), BUFFER_TOO_SMALL),
+    "pol-stride-one-short": (lambda K, C: (K, K * C - 1, False), INVALID_ARG),
+    "null-out": (lambda K, C: (K, K * C, True), INVALID_ARG),
+}
+
+
+def _lowcbf_rejected_case(dev, entry, reject):
+    """A fresh LowCBF plan whose FIRST call is rejected, then the corrected call: the one-time
+    1536-zero pre-padding (polyphase_analysis_lowcbf.m:27-34) must still be pending — the
+    length query unchanged, the output bit-identical to a twin plan that never saw the
+    rejected call and equal to the oracle with do_padding=True.  (The parent consumed the
+    padding in the rejected call: the retry then returned K - 8 rows of unpadded data.)"""
+    import torch
+    pfb, lib = _pfb(), _lib()
+    taps = pfb.read_fir_filter_coeff(pfb.config.config_dir + "/PST_filtertaps.txt")
+    n_pol, C = 2, 216
+    n_dat = 3072 - 1536 + 192 * 20 + 7
+    K = 20  # floor((n_dat + 1536 - 3072) / 192), a multiple of nu = 4: no row trimmed
+    x = _noise(np.random.default_rng(301), (n_pol, n_dat))
+    plan = pfb.AnalysisPlan(taps, 256, "4/3", "polyphase_analysis_lowcbf", n_pol, 0)
+    twin = pfb.AnalysisPlan(taps, 256, "4/3", "polyphase_analysis_lowcbf", n_pol, 0)
+    assert plan.out_chan == C
+    if entry == "analysis":
+        fn, query = lib.pfb_analysis_execute, lambda p: int(lib.pfb_analysis_output_length(p._h, n_dat))
+    else:
+        fn, query = lib.pfb_filterbank_execute, lambda p: int(lib.pfb_filterbank_output_rows(p._h, n_dat))
+
+    def call(p, fout, cap, out_ps, null=False):
+        n = c_int64(-1)
+        st = fn(p._h, c_void_p(fin.ptr), fin.stride, n_dat, c_void_p(0 if null else fout.ptr), out_ps, cap,
+                byref(n), DEVICE, _stream(dev))
+        torch.cuda.synchronize(dev)
+        return st, int(n.value)
+
+    fin = _Frame(dev, n_pol, n_dat, fill=NAN).put(x)
+    assert query(plan) == K and query(twin) == K
+    layout, status = LOWCBF_REJECTS[reject]
+    cap, out_ps, null = layout(K, C)
+    bad = _Frame(dev, n_pol, K * C)
+    st, n = call(plan, bad, cap, out_ps, null)
+    assert st == status, (st, _err(lib))
+    assert bad.guards_intact(0), "a rejected call wrote output"
+    assert query(plan) == K, "a rejected call changed the length query (pre-padding consumed)"
+    assert plan.buffered_samples == 0
+    good, ref_out = _Frame(dev, n_pol, K * C), _Frame(dev, n_pol, K * C)
+    st, n = call(plan, good, K, K * C)
+    assert st == OK and n == K, (st, n, _err(lib))
+    st, n = call(twin, ref_out, K, K * C)
+    assert st == OK and n == K, (st, n, _err(lib))
+    got = good.get(K * C)
+    assert _no_nan(got)
+    assert _same_bits(got, ref_out.get(K * C)), "the call after a rejected one differs from a first call"
+    ref = orc.polyphase_analysis_lowcbf(x[:, None, :], taps, do_padding=True)
+    assert ref.shape == (n_pol, C, K)
+    assert_pfb_close(got.cpu().numpy().reshape(n_pol, K, C).transpose(0, 2, 1), ref,
+                     what=f"lowcbf {entry} after {reject}")
+    # and the padding is consumed exactly once: the next query is the unpadded one
+    assert query(plan) == query(twin)
+    assert plan.buffered_samples == twin.buffered_samples
+
+
+@pytest.mark.parametrize("reject", list(LOWCBF_REJECTS))
+def test_analysis_lowcbf_rejected_call_keeps_padding(gpu, reject):
+    """pfb_analysis_execute on a fresh LowCBF plan, first call rejected for (a) a capacity one
+    row short (PFB_ERR_BUFFER_TOO_SMALL), (b) an out_pol_stride one element short, (c) a null
+    output (both PFB_ERR_INVALID_ARG): see _lowcbf_rejected_case."""
+    _lowcbf_rejected_case(gpu, "analysis", reject)
+
+
+def test_filterbank_lowcbf_rejected_call_keeps_padding(gpu):
+    """pfb_filterbank_execute on a fresh LowCBF plan, first call rejected for a capacity one
+    row short (PFB_ERR_BUFFER_TOO_SMALL; filterbank_exec's generic branch): nothing buffered,
+    the padding still pending, the corrected call equal to a first call."""
+    _lowcbf_rejected_case(gpu, "filterbank", "capacity-one-row-short")
+
+
 # ----------------------------------------------------------------------------- synthesis
 SYNTH_LAYOUTS = [
     # inp: (lead, a, b rows, tail); out: (lead, gap, tail, extra capacity in samples)
