@@ -336,6 +336,39 @@ pfb_status pfb_dada_unpack(const void* in, int32_t nbit, int32_t ndim, int32_t o
                            int64_t n_dat, int32_t n_chan, int32_t n_pol, pfb_cf32* out,
                            int64_t out_pol_stride, void* stream);
 
+/* Synthesis straight from a DADA data section (DADARead.m:58-83 followed by
+ * InverseFilterBank.m:92-96 / polyphase_synthesis).  Device memory only.  `in` holds n_dat
+ * (n_in) rows x the plan's n_chan x n_pol x ndim values of nbit, in `order` (pfb_dada_order).
+ * The result, *n_out, the status codes, pfb_inverse_filterbank_buffered and the stream state
+ * are those of pfb_dada_unpack into a packed buffer followed by pfb_synthesis_execute /
+ * pfb_inverse_filterbank_execute, bit for bit.  Every check (NBIT 8/16/32/64, NDIM 1/2, the
+ * order, LowCBF rows a multiple of 32, null buffers, and the capacity and stride checks of
+ * the cf32 calls) runs before any launch or state change: a rejected stream call leaves the
+ * carry untouched.
+ * FUSED: the channel IFFT reads the section's own bytes (NBIT 8/16, NDIM 2, a section
+ * aligned to a complex sample, channel counts below 4096, a plan without combine
+ * permutation, temporal-taper gain or spectral taper) and the unpacked samples never cross
+ * HBM.  A stream call reads the blocks made of new rows only in place; the blocks that
+ * start in the carry are stitched from the cf32 carry and the unpacked head of the section,
+ * and the new carry is the unpacked tail.  STAGED: any other plan or format is unpacked into
+ * a plan-owned buffer and runs the cf32 path.  pfb_synthesis_last_dada_input: which of the
+ * two the plan's last DADA call took (FUSED when any of its channel IFFTs read the section
+ * in place), NONE before one or after a cf32 call, -1 for a null plan. */
+typedef enum pfb_dada_input {
+  PFB_DADA_INPUT_NONE = 0,
+  PFB_DADA_INPUT_FUSED = 1,
+  PFB_DADA_INPUT_STAGED = 2
+} pfb_dada_input;
+pfb_status pfb_synthesis_execute_dada(pfb_synthesis_plan* plan, const void* in, int32_t nbit,
+                                      int32_t ndim, int32_t order, int64_t n_dat,
+                                      int64_t sample_offset, pfb_cf32* out, int64_t out_pol_stride,
+                                      int64_t out_capacity, int64_t* n_out, void* stream);
+pfb_status pfb_inverse_filterbank_execute_dada(pfb_synthesis_plan* plan, const void* in,
+                                               int32_t nbit, int32_t ndim, int32_t order,
+                                               int64_t n_in, pfb_cf32* out, int64_t out_pol_stride,
+                                               int64_t out_capacity, int64_t* n_out, void* stream);
+int32_t pfb_synthesis_last_dada_input(const pfb_synthesis_plan* plan);
+
 /* [pol][t][chan] complex float32 -> DADA TFP data section (NDIM 2) of NBIT 8/16/32/64;
  * integer types follow Matlab's cast (round half away from zero, saturate).  Replaces
  * write_dada_data.m:32-50 (data written with the class write_dada_header.m:13-22

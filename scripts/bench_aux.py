@@ -6,6 +6,8 @@ one MI355X, as algorithmic HBM bytes / time against the 8 TB/s peak.
   * LowCBF PST filterbank (polyphase_analysis_lowcbf, 2^24 samples x 2 pol)
   * DADA unpack (NBIT 8 / 32) and pack, corner turn, channel gather, quantisation
   * two-stage analysis cascade (256 x 256 ch; stage 2 batched over 256 series)
+  * --only-dada: synthesis from a DADA section at the C2 shape, the staged pair
+    (pfb_dada_unpack + pfb_synthesis_execute) against pfb_synthesis_execute_dada, interleaved
 
 Prints one JSON object per line.  Usage: python scripts/bench_aux.py [--reps N]
 """
@@ -47,6 +49,9 @@ def main():
     ap.add_argument("--skip-mid", action="store_true")
     ap.add_argument("--only-mid", action="store_true")
     ap.add_argument("--only-twostage", action="store_true")
+    ap.add_argument("--only-dada", action="store_true",
+                    help="the dada_synthesis A/B alone (--reps: calls per timed window)")
+    ap.add_argument("--rounds", type=int, default=15, help="--only-dada: interleaved A/B windows per case")
     ap.add_argument("--padded-cascade", default="default",
                     choices=["default", "strided", "no-stage1", "no-stage2", "gather"],
                     help="the SKA-Mid padded cascade's stores: the library default; both stages strided; "
@@ -76,6 +81,8 @@ def main():
                    graph=bool(args.graph))
     if args.only_twostage:
         return twostage(torch, pfb, noise, args.reps, args.padded_cascade)
+    if args.only_dada:
+        return dada_synthesis(torch, pfb, dev, max(args.reps, 20), args.rounds)
     # ---- C2' (4/3) round trip
     taps43 = pfb.design_PFB_FIR_filter(256, "4/3", 12)
     n = 1 << 24
@@ -171,6 +178,72 @@ def twostage(torch, pfb, noise, reps, padded_cascade="default"):
          note="both stages polyphase_analysis_padded; bytes: the two analyses' input+output",
          **({} if stages is None else {"padded_cascade": padded_cascade}))
     del xm, tm
+
+
+def dada_synthesis(torch, pfb, dev, reps, rounds):
+    """DADA section -> series at the C2 synthesis shape (256 ch, 8/7, Nf 256, Ov 48, tukey,
+    deripple; the rows of a 2^24-sample unit).  A: pfb_dada_unpack into a cf32 buffer, then
+    pfb_synthesis_execute (the calls a caller had before).  B: pfb_synthesis_execute_dada.
+    The outputs are asserted equal first; then `rounds` windows of `reps` calls of each side,
+    alternating A and B in one process, after a warm-up of both.  One line per case with the
+    median, min, max and quartiles of each side's per-call time over the windows."""
+    from ctypes import c_void_p
+    from ska_pst_dsp_model_amd import _lib
+    lib = _lib.load()
+    N, rows = 256, ((1 << 24) // 224) // 32 * 32     # whole LowCBF heaps: 74 880 rows
+    taps = pfb.design_PFB_FIR_filter(N, "8/7", 12)
+    win = pfb.PFBWindow().lookup["tukey"](256, 48)
+    g = torch.Generator(device=dev).manual_seed(2)
+    for n_pol in (1, 2):
+        syn = pfb.SynthesisPlan(N, "8/7", 256, 48, True, 1, True, taps, win, None, n_pol)
+        out_a = torch.empty((n_pol, syn.output_length(rows)), dtype=torch.complex64, device=dev)
+        out_b = torch.empty_like(out_a)
+        x = torch.empty((n_pol, rows, N), dtype=torch.complex64, device=dev)
+        for nbit, lowcbf in ((16, False), (16, True), (8, False)):
+            dt = torch.int16 if nbit == 16 else torch.int8
+            lim = 1 << (nbit - 1)
+            raw = torch.randint(-lim, lim, (rows * N * n_pol * 2,), dtype=dt, device=dev, generator=g)
+            order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
+            stream = c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+            def side_a():
+                _lib.check(lib.pfb_dada_unpack(c_void_p(raw.data_ptr()), nbit, 2, order, rows, N, n_pol,
+                                               c_void_p(x.data_ptr()), rows * N, stream))
+                syn.execute(x, layout="ptc", out=out_a)
+
+            def side_b():
+                syn.execute_dada(raw, nbit, lowcbf=lowcbf, out=out_b)
+
+            side_a()
+            side_b()
+            path = syn.last_dada_input()
+            torch.cuda.synchronize()
+            assert torch.equal(out_a, out_b), f"dada_synthesis {nbit} lowcbf={lowcbf}: outputs differ"
+            for _ in range(2):
+                timeit(torch, side_a, reps)
+                timeit(torch, side_b, reps)
+            ta, tb = [], []
+            for _ in range(rounds):
+                ta.append(timeit(torch, side_a, reps))
+                tb.append(timeit(torch, side_b, reps))
+
+            def stats(t):
+                q = np.percentile(t, [0, 25, 50, 75, 100])
+                return {k: round(float(v), 4) for k, v in zip(("min", "q25", "median", "q75", "max"), q)}
+            a, b = stats(ta), stats(tb)
+            samples = rows * N * n_pol
+            print(json.dumps({
+                "kernel": "dada_synthesis", "shape": "256ch 8/7 Nf256 Ov48 tukey deripple", "rows": rows,
+                "n_pol": n_pol, "nbit": nbit, "order": "lowcbf" if lowcbf else "tfp", "path": path,
+                "calls_per_window": reps, "windows": rounds, "outputs_equal": True,
+                "A_unpack_then_execute_ms": a, "B_execute_dada_ms": b,
+                "A_spread_ms": round(a["max"] - a["min"], 4),
+                "B_below_A_by_ms": round(a["median"] - b["median"], 4),
+                "B_over_A": round(b["median"] / a["median"], 4),
+                "A_first_pass_bytes_per_sample": 2 * nbit // 8 + 8 + 8,
+                "B_first_pass_bytes_per_sample": 2 * nbit // 8,
+                "samples": samples}), flush=True)
+        del syn, out_a, out_b, x
 
 
 def cpu_baselines(pfb):

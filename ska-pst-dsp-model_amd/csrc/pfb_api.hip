@@ -897,6 +897,7 @@ struct pfb_synthesis_plan {
   int chunk_blocks = 0;
   int stage1 = PFB_STAGE1_AUTO;  // pfb_synthesis_set_stage1_rows
   int last_stage1 = 0;           // pfb_synthesis_last_stage1_rows: where the last launch got its rows
+  int last_dada = PFB_DADA_INPUT_NONE;  // pfb_synthesis_last_dada_input
   int rt_chunk_blocks = 64;  // round-trip pipeline chunk (PFB_RT_CHUNK_BLOCKS)
   int timing_mask = 0;  // PFB_TIMING_MASK (timing experiments; results invalid when set)
   int ranges = -1;  // PFB_SYNTH_RANGES: 0 one workgroup per block, -1 persistent auto, >0 persistent
@@ -1015,10 +1016,13 @@ static pfb_status synthesis_spectral(pfb_synthesis_plan* p, const float2* in, in
 // call whose carried rows are not in front of it; blocks b0.. must not read before it.  A
 // negative row_shift: block 0 starts -row_shift rows into `in` (InverseFilterBank's
 // sample_offset applied to the concatenated rows))
+// (dada: the call's rows are a DADA section read in place, `in` is unused — the section's
+// row 0 is the call's row row_shift)
 static pfb_status synthesis_chunk(pfb_synthesis_plan* p, const float2* in, int64_t in_ps, int64_t b0,
                                   int64_t nb, float2* out, int64_t out_ps, int64_t out_limit,
-                                  hipStream_t s, int64_t row_shift = 0) {
+                                  hipStream_t s, int64_t row_shift = 0, const pfb::DadaIn* dada = nullptr) {
   if (p->has_spectral) {
+    if (dada) return fail(PFB_ERR_UNSUPPORTED, "DADA rows with a spectral taper");
     // (a negative row shift: the blocks start -row_shift rows into `in` — a sample offset)
     if (row_shift > 0) return fail(PFB_ERR_UNSUPPORTED, "row shift with a spectral taper");
     return synthesis_spectral(p, in + (-row_shift) * p->N, in_ps, b0, nb, out, out_ps, out_limit, s);
@@ -1028,7 +1032,16 @@ static pfb_status synthesis_chunk(pfb_synthesis_plan* p, const float2* in, int64
   HIPCHK(p->Z.ensure((size_t)p->n_pol * rows * p->N * sizeof(float2)));
   float2* Z = p->Z.as<float2>();
   pfb::ChanIfftArgs c{};
-  c.in = in + (b0 * p->keep - row_shift) * p->N;
+  pfb::DadaIn dd{};
+  if (dada) {
+    dd = *dada;
+    dd.t0 = b0 * p->keep - row_shift;
+    if (dd.t0 < 0 || dd.t0 + rows > dd.n_dat) return fail(PFB_ERR_INVALID_ARG, "rows outside the DADA section");
+    c.dada = &dd;
+    p->last_dada = PFB_DADA_INPUT_FUSED;
+  } else {
+    c.in = in + (b0 * p->keep - row_shift) * p->N;
+  }
   c.in_pol_stride = in_ps;
   c.out = Z;
   c.out_pol_stride = rows * p->N;
@@ -1044,7 +1057,8 @@ static pfb_status synthesis_chunk(pfb_synthesis_plan* p, const float2* in, int64
   const int zb = pfb::synth_wave_supported(synth_args(p, Z, rows * p->N, b0, nb, out, out_ps, out_limit, 2)) ? 2 : 0;
   c.zblk = zb ? zb : 1;
   {
-    ProfScope ps(1, (double)p->n_pol * rows * p->N * 16.0, s);
+    const double in_bytes = dada ? 2.0 * (dada->nbit / 8) : 8.0;
+    ProfScope ps(1, (double)p->n_pol * rows * p->N * (in_bytes + 8.0), s);
     HIPCHK(pfb::launch_chan_ifft(c, s));
   }
   return synthesis_blocks(p, Z, rows * p->N, b0, nb, out, out_ps, out_limit, s, zb);
@@ -1124,12 +1138,12 @@ static int64_t synthesis_chunk_blocks(const pfb_synthesis_plan* p, int64_t B) {
 // blocks [b_lo, b_hi) in chunks (see synthesis_chunk for row_shift)
 static pfb_status synthesis_range(pfb_synthesis_plan* p, const float2* in, int64_t in_ps, int64_t b_lo,
                                   int64_t b_hi, float2* out, int64_t out_ps, int64_t out_limit,
-                                  hipStream_t s, int64_t row_shift = 0) {
+                                  hipStream_t s, int64_t row_shift = 0, const pfb::DadaIn* dada = nullptr) {
   if (b_hi <= b_lo) return PFB_OK;
   const int64_t CB = synthesis_chunk_blocks(p, b_hi - b_lo);
   for (int64_t b0 = b_lo; b0 < b_hi; b0 += CB) {
     pfb_status st = synthesis_chunk(p, in, in_ps, b0, std::min<int64_t>(CB, b_hi - b0), out, out_ps,
-                                    out_limit, s, row_shift);
+                                    out_limit, s, row_shift, dada);
     if (st != PFB_OK) return st;
   }
   return PFB_OK;
@@ -1463,14 +1477,51 @@ pfb_status pfb_synthesis_set_chunk_blocks(pfb_synthesis_plan* p, int32_t blocks)
   return PFB_OK;
 }
 
-pfb_status pfb_synthesis_execute(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
-                                 int64_t n_dat, int64_t sample_offset, pfb_cf32* out,
-                                 int64_t out_ps, int64_t cap, int64_t* n_out, int32_t mem,
-                                 void* stream) {
+// A DADA data section as the input of a synthesis call (pfb_synthesis_execute_dada,
+// pfb_inverse_filterbank_execute_dada): rows x the plan's n_chan x n_pol x ndim values of nbit
+struct DadaSection {
+  const void* base;
+  int nbit, ndim, order;
+};
+
+static pfb_status dada_section_check(const pfb_synthesis_plan* p, const DadaSection& sec, int64_t rows) {
+  if (!p) return fail(PFB_ERR_INVALID_ARG, "null plan");
+  if (sec.nbit != 8 && sec.nbit != 16 && sec.nbit != 32 && sec.nbit != 64)
+    return fail(PFB_ERR_INVALID_ARG, "NBIT must be 8, 16, 32 or 64");
+  if (sec.ndim != 1 && sec.ndim != 2) return fail(PFB_ERR_INVALID_ARG, "NDIM must be 1 or 2");
+  if (sec.order != PFB_DADA_TFP && sec.order != PFB_DADA_LOWCBF)
+    return fail(PFB_ERR_INVALID_ARG, "unknown sample order");
+  if (sec.order == PFB_DADA_LOWCBF && rows > 0 && rows % 32)
+    return fail(PFB_ERR_INVALID_ARG, "LowCBF data are heaps of 32 samples");
+  return PFB_OK;
+}
+
+// the channel IFFT can read the section in place (pfb_api.h, FUSED)
+static bool dada_fusable(const pfb_synthesis_plan* p, const DadaSection& sec) {
+  return sec.ndim == 2 && pfb::chan_ifft_dada_supported(p->N, sec.nbit) && p->identity_perm && !p->has_cgain &&
+         !p->has_spectral && reinterpret_cast<uintptr_t>(sec.base) % (size_t)(sec.nbit / 4) == 0;
+}
+
+// STAGED: the section's `rows` rows unpacked into the plan's staging buffer ([pol][row][chan],
+// pol stride rows N)
+static pfb_status dada_stage(pfb_synthesis_plan* p, const DadaSection& sec, int64_t rows, hipStream_t s) {
+  HIPCHK(p->stage_in.ensure((size_t)p->n_pol * std::max<int64_t>(rows, 1) * p->N * sizeof(float2)));
+  p->last_dada = PFB_DADA_INPUT_STAGED;
+  return pfb_dada_unpack(sec.base, sec.nbit, sec.ndim, sec.order, rows, p->N, p->n_pol,
+                         reinterpret_cast<pfb_cf32*>(p->stage_in.p), rows * p->N, s);
+}
+
+// pfb_synthesis_execute; sec: the rows are a DADA section (device memory) instead of `in`
+static pfb_status synthesis_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
+                                 const DadaSection* sec, int64_t n_dat, int64_t sample_offset,
+                                 pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
+                                 int32_t mem, void* stream) {
+  if (sec) in = static_cast<const pfb_cf32*>(sec->base);
   if (!p || (!in && n_dat > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
   if (sample_offset < 1) return fail(PFB_ERR_INVALID_ARG, "sample_offset is 1-based (>= 1)");
   if (n_dat < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_dat");
   HIPCHK(hipSetDevice(p->device));
+  p->last_dada = PFB_DADA_INPUT_NONE;
   hipStream_t s = (hipStream_t)stream;
   const int64_t off = std::min<int64_t>(sample_offset - 1, std::max<int64_t>(n_dat, 0));
   const int64_t n = n_dat - off;  // in = in(:, :, sample_offset:end)  (:99)
@@ -1481,8 +1532,19 @@ pfb_status pfb_synthesis_execute(pfb_synthesis_plan* p, const pfb_cf32* in, int6
   if (cap < olen) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld",
                               (long long)cap, (long long)olen);
   if (mem == PFB_MEM_DEVICE) {
-    if (in_ps < n_dat * p->N || out_ps < olen)
+    if ((!sec && in_ps < n_dat * p->N) || out_ps < olen)
       return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
+    if (sec) {
+      if (dada_fusable(p, *sec)) {
+        // the blocks start `off` rows into the section (a negative row shift)
+        const pfb::DadaIn d{sec->base, sec->nbit, sec->order == PFB_DADA_LOWCBF, n_dat, 0};
+        return synthesis_range(p, nullptr, 0, 0, synth_blocks(p, n), (float2*)out, out_ps, olen, s, -off, &d);
+      }
+      const pfb_status st = dada_stage(p, *sec, n_dat, s);
+      if (st != PFB_OK) return st;
+      in = reinterpret_cast<const pfb_cf32*>(p->stage_in.p);
+      in_ps = n_dat * p->N;
+    }
     return synthesis_run(p, (const float2*)in + off * p->N, in_ps, n, (float2*)out, out_ps, olen, s);
   }
   HIPCHK(p->stage_in.ensure((size_t)p->n_pol * n * p->N * sizeof(float2)));
@@ -1498,6 +1560,25 @@ pfb_status pfb_synthesis_execute(pfb_synthesis_plan* p, const pfb_cf32* in, int6
   return PFB_OK;
 }
 
+pfb_status pfb_synthesis_execute(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
+                                 int64_t n_dat, int64_t sample_offset, pfb_cf32* out,
+                                 int64_t out_ps, int64_t cap, int64_t* n_out, int32_t mem,
+                                 void* stream) {
+  return synthesis_exec(p, in, in_ps, nullptr, n_dat, sample_offset, out, out_ps, cap, n_out, mem, stream);
+}
+
+pfb_status pfb_synthesis_execute_dada(pfb_synthesis_plan* p, const void* in, int32_t nbit, int32_t ndim,
+                                      int32_t order, int64_t n_dat, int64_t sample_offset, pfb_cf32* out,
+                                      int64_t out_ps, int64_t cap, int64_t* n_out, void* stream) {
+  const DadaSection sec{in, nbit, ndim, order};
+  const pfb_status st = dada_section_check(p, sec, n_dat);
+  if (st != PFB_OK) return st;
+  return synthesis_exec(p, nullptr, 0, &sec, n_dat, sample_offset, out, out_ps, cap, n_out, PFB_MEM_DEVICE,
+                        stream);
+}
+
+int32_t pfb_synthesis_last_dada_input(const pfb_synthesis_plan* p) { return p ? p->last_dada : -1; }
+
 pfb_status pfb_inverse_filterbank_set_sample_offset(pfb_synthesis_plan* p, int64_t sample_offset) {
   if (!p) return fail(PFB_ERR_INVALID_ARG, "null plan");
   if (sample_offset < 0) return fail(PFB_ERR_INVALID_ARG, "sample_offset is 0-based (>= 0)");
@@ -1510,12 +1591,18 @@ pfb_status pfb_inverse_filterbank_set_sample_offset(pfb_synthesis_plan* p, int64
 // carry starts at input_idat = (output length) nu / (n_chan de) = B keep of the
 // concatenation — not offset by `so`: the next call skips `so` rows of it again, so
 // consecutive calls see the blocks of one continuous run.
-pfb_status pfb_inverse_filterbank_execute(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
-                                          int64_t n_in, pfb_cf32* out, int64_t out_ps, int64_t cap,
-                                          int64_t* n_out, int32_t mem, void* stream) {
+// (sec: the new rows are a DADA section in device memory instead of `in`.  Fusable: the
+// blocks of new rows read it in place, and whatever the cf32 call copies out of `in` — the
+// stitched head, the carry — is unpacked from the section's rows instead.  Otherwise the
+// section is unpacked whole once every check has passed, and the cf32 path runs.)
+static pfb_status ifb_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps, const DadaSection* sec,
+                           int64_t n_in, pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
+                           int32_t mem, void* stream) {
+  if (sec) in = static_cast<const pfb_cf32*>(sec->base);
   if (!p || (!in && n_in > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
   if (n_in < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_in");
   HIPCHK(hipSetDevice(p->device));
+  p->last_dada = PFB_DADA_INPUT_NONE;
   hipStream_t s = (hipStream_t)stream;
   const int N = p->N;
   const int64_t total = p->buffered + n_in;
@@ -1545,8 +1632,33 @@ pfb_status pfb_inverse_filterbank_execute(pfb_synthesis_plan* p, const pfb_cf32*
   if (n_out) *n_out = olen;
   if (olen > cap) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld",
                               (long long)cap, (long long)olen);
-  if (mem == PFB_MEM_DEVICE && (in_ps < n_in * N || out_ps < olen))
+  if (mem == PFB_MEM_DEVICE && ((!sec && in_ps < n_in * N) || out_ps < olen))
     return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
+  if (olen > 0 && !out) return fail(PFB_ERR_INVALID_ARG, "null output");
+  pfb::DadaIn dd{};
+  const pfb::DadaIn* dada = nullptr;
+  if (sec) {
+    if (dada_fusable(p, *sec)) {
+      dd = pfb::DadaIn{sec->base, sec->nbit, sec->order == PFB_DADA_LOWCBF, n_in, 0};
+      dada = &dd;
+      in = nullptr;
+    } else {
+      const pfb_status st = dada_stage(p, *sec, n_in, s);
+      if (st != PFB_OK) return st;
+      in = reinterpret_cast<const pfb_cf32*>(p->stage_in.p);
+      in_ps = n_in * N;
+    }
+  }
+  // rows [row0, row0 + n) of the new input -> dst[pol][0, n N)
+  auto rows_to = [&](float2* dst, int64_t dps, int64_t row0, int64_t n) -> hipError_t {
+    if (dada) {
+      pfb::DadaIn d = dd;
+      d.t0 = row0;
+      if (p->last_dada == PFB_DADA_INPUT_NONE) p->last_dada = PFB_DADA_INPUT_STAGED;
+      return pfb::launch_dada_unpack_rows(d, n, N, p->n_pol, dst, dps, s);
+    }
+    return copy_pols(dst, dps, (const float2*)in + row0 * N, in_ps, n * N, p->n_pol, kin, s);
+  };
   {
     // Carry without the concatenation copy: blocks whose rows start at or after the
     // carried Bc rows read the new input in place (row shift Bc - so), the first ones a
@@ -1563,20 +1675,17 @@ pfb_status pfb_inverse_filterbank_execute(pfb_synthesis_plan* p, const pfb_cf32*
           float2* wk = p->work.as<float2>();
           HIPCHK(copy_pols(wk, L * N, p->carry.as<float2>(), Bc * N, std::min(Bc, L) * N, p->n_pol,
                            hipMemcpyDeviceToDevice, s));
-          if (L > Bc)
-            HIPCHK(copy_pols(wk + Bc * N, L * N, (const float2*)in, in_ps, (L - Bc) * N, p->n_pol,
-                             hipMemcpyDeviceToDevice, s));
+          if (L > Bc) HIPCHK(rows_to(wk + Bc * N, L * N, 0, L - Bc));
           pfb_status st = synthesis_range(p, wk, L * N, 0, b_s, (float2*)out, out_ps, olen, s, -so);
           if (st != PFB_OK) return st;
         }
-        pfb_status st =
-            synthesis_range(p, (const float2*)in, in_ps, b_s, B, (float2*)out, out_ps, olen, s, Bc - so);
+        pfb_status st = synthesis_range(p, (const float2*)in, in_ps, b_s, B, (float2*)out, out_ps, olen, s,
+                                        Bc - so, dada);
         if (st != PFB_OK) return st;
       }
       if (buffered > 0) {
         HIPCHK(p->carry.ensure((size_t)p->n_pol * buffered * N * sizeof(float2)));
-        HIPCHK(copy_pols(p->carry.as<float2>(), buffered * N, (const float2*)in + (input_idat - Bc) * N, in_ps,
-                         buffered * N, p->n_pol, hipMemcpyDeviceToDevice, s));
+        HIPCHK(rows_to(p->carry.as<float2>(), buffered * N, input_idat - Bc, buffered));
       }
       p->buffered = std::max<int64_t>(buffered, 0);
       return PFB_OK;
@@ -1588,13 +1697,25 @@ pfb_status pfb_inverse_filterbank_execute(pfb_synthesis_plan* p, const pfb_cf32*
   if (p->buffered == 0 && mem == PFB_MEM_DEVICE) {
     w = (const float2*)in;
     wps = in_ps;
+    if (dada) {
+      // nothing carried: every block reads the section in place, the carry is its unpacked tail
+      if (olen > 0) {
+        pfb_status st = synthesis_range(p, nullptr, 0, 0, B, (float2*)out, out_ps, olen, s, -so, dada);
+        if (st != PFB_OK) return st;
+      }
+      if (buffered > 0) {
+        HIPCHK(p->carry.ensure((size_t)p->n_pol * buffered * N * sizeof(float2)));
+        HIPCHK(rows_to(p->carry.as<float2>(), buffered * N, input_idat, buffered));
+      }
+      p->buffered = std::max<int64_t>(buffered, 0);
+      return PFB_OK;
+    }
   } else {
     HIPCHK(p->work.ensure((size_t)p->n_pol * std::max<int64_t>(total, 1) * N * sizeof(float2)));
     float2* wk = p->work.as<float2>();
     HIPCHK(copy_pols(wk, total * N, p->carry.as<float2>(), p->buffered * N, p->buffered * N, p->n_pol,
                      hipMemcpyDeviceToDevice, s));
-    HIPCHK(copy_pols(wk + p->buffered * N, total * N, (const float2*)in, in_ps, n_in * N, p->n_pol,
-                     kin, s));
+    HIPCHK(rows_to(wk + p->buffered * N, total * N, 0, n_in));
     w = wk;
     wps = total * N;
   }
@@ -1618,6 +1739,21 @@ pfb_status pfb_inverse_filterbank_execute(pfb_synthesis_plan* p, const pfb_cf32*
   p->buffered = std::max<int64_t>(buffered, 0);
   if (mem == PFB_MEM_HOST) HIPCHK(hipStreamSynchronize(s));
   return PFB_OK;
+}
+
+pfb_status pfb_inverse_filterbank_execute(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
+                                          int64_t n_in, pfb_cf32* out, int64_t out_ps, int64_t cap,
+                                          int64_t* n_out, int32_t mem, void* stream) {
+  return ifb_exec(p, in, in_ps, nullptr, n_in, out, out_ps, cap, n_out, mem, stream);
+}
+
+pfb_status pfb_inverse_filterbank_execute_dada(pfb_synthesis_plan* p, const void* in, int32_t nbit,
+                                               int32_t ndim, int32_t order, int64_t n_in, pfb_cf32* out,
+                                               int64_t out_ps, int64_t cap, int64_t* n_out, void* stream) {
+  const DadaSection sec{in, nbit, ndim, order};
+  const pfb_status st = dada_section_check(p, sec, n_in);
+  if (st != PFB_OK) return st;
+  return ifb_exec(p, nullptr, 0, &sec, n_in, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream);
 }
 
 int64_t pfb_inverse_filterbank_buffered(const pfb_synthesis_plan* p) { return p ? p->buffered : -1; }

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace pfb {
 
@@ -288,6 +289,30 @@ struct RowLoad {
   }
 };
 
+// RowLoad's twin for rows that are still a DADA data section (T = int8_t / int16_t, NDIM 2):
+// element (row, i) of polarisation `pol` is file element (t0 + row, c, pol) — dada_index —
+// fetched as ONE 2- or 4-byte load (char2 / short2) and cast; the cast is exact, so the value
+// is the one pfb_dada_unpack would have stored for RowLoad to read.  Same clamp: no lane reads
+// past file row t0 + last.  The section must be aligned to a complex sample (2 sizeof(T)).
+template <class T, bool LOWCBF, bool PERM, bool GAIN>
+struct RowLoadDada {
+  static constexpr bool kIsLds = false;
+  using Pair = std::conditional_t<sizeof(T) == 1, char2, short2>;
+  const Pair* in;
+  int64_t r0, last, t0;
+  int N, P, pol;
+  const int* perm;
+  const float* cgain;
+  __device__ __forceinline__ float2 load(int row, int i) const {
+    const int64_t r = min(r0 + row, last);
+    const int c = PERM ? perm[i] : i;
+    const Pair s = in[dada_index<LOWCBF>(t0 + r, c, pol, N, P)];
+    float2 v = make_float2((float)s.x, (float)s.y);
+    if constexpr (GAIN) v = cscale(v, cgain[c]);
+    return v;
+  }
+};
+
 struct RowStore {
   static constexpr bool kIsLds = false;
   float2* out;
@@ -375,6 +400,27 @@ struct RowShape {
   static constexpr int RS = lds_row(N);
 };
 
+// One workgroup's ROWS rows through block_fft: rows in through `ld`, out through `st`
+// (shared by row_fft_kernel and row_fft_dada_kernel)
+template <int N, int DIR, class Load, class Store>
+__device__ __forceinline__ void row_fft_tile(const Load& ld, const Store& st, const float2* tw_g, float2* smem) {
+  constexpr int ROWS = RowShape<N>::ROWS;
+  LdsRows rows(smem, RowShape<N>::RS);
+  // twiddle table -> LDS behind the rows (ordered before pass 2 by its barrier)
+  float2* tw = smem + ROWS * RowShape<N>::RS;
+  constexpr int TPT = (N + NT - 1) / NT;
+  float2 twv[TPT];
+#pragma unroll
+  for (int i = 0; i < TPT; ++i) {
+    const int m = threadIdx.x + i * NT;
+    twv[i] = tw_g[m < N ? m : 0];
+  }
+#pragma unroll
+  for (int i = 0; i < TPT; ++i)
+    if (threadIdx.x + i * NT < N) tw[tw_slot(threadIdx.x + i * NT)] = twv[i];
+  block_fft<N, DIR, ROWS, NT>(ld, st, rows, tw, threadIdx.x);
+}
+
 // STRIDED: the rows go out through RowStridedStore (a.out_rs > 0) instead of RowStore
 template <int N, int DIR, bool PERM, bool GAIN, bool STRIDED = false>
 __global__ __launch_bounds__(NT) void row_fft_kernel(RowFftArgs a) {
@@ -391,20 +437,42 @@ __global__ __launch_bounds__(NT) void row_fft_kernel(RowFftArgs a) {
       return RowStore{a.out + pol * a.out_pol_stride, r0, a.n_rows, N, a.sds, a.remap, a.scale,
                       a.row_base, a.n_total, a.zs, a.nt};
   }();
-  LdsRows rows(smem, RowShape<N>::RS);
-  // twiddle table -> LDS behind the rows (ordered before pass 2 by its barrier)
-  float2* tw = smem + ROWS * RowShape<N>::RS;
-  constexpr int TPT = (N + NT - 1) / NT;
-  float2 twv[TPT];
-#pragma unroll
-  for (int i = 0; i < TPT; ++i) {
-    const int m = threadIdx.x + i * NT;
-    twv[i] = a.tw[m < N ? m : 0];
-  }
-#pragma unroll
-  for (int i = 0; i < TPT; ++i)
-    if (threadIdx.x + i * NT < N) tw[tw_slot(threadIdx.x + i * NT)] = twv[i];
-  block_fft<N, DIR, ROWS, NT>(ld, st, rows, tw, threadIdx.x);
+  row_fft_tile<N, DIR>(ld, st, a.tw, smem);
+}
+
+// Workgroup -> (tile, pol) of row_fft_dada_kernel.  Workgroups that fetch the same lines of
+// the section are put on ONE XCD, consecutively, so the second one finds the lines in that
+// XCD's L2: the two polarisations of a tile (TFP interleaves them at sample granularity) and,
+// in LowCBF order, the tiles of one heap (a tile of ROWS < 32 rows uses ROWS of the 32
+// samples of every (heap, chan, pol) line).  Workgroups b and b + 8 share an XCD: within a
+// group of 8 `share` workgroups, slot = (b mod 8) share + (b div 8), tile = slot / P, pol =
+// slot mod P.  Groups follow each other in blockIdx order, so the chip's loads in flight stay
+// in one window of the rows.  Bijective on the grid (a multiple of 8 share); slots past the
+// last tile return.  share = 1: blockIdx order.
+struct DadaRows {
+  const void* base;
+  int64_t t0, tiles;
+  int P, share;
+};
+
+// row_fft_kernel<N, +1, PERM, GAIN> with the rows read from a DADA section (RowLoadDada):
+// same passes, tables and RowStore, so the Z rows are bit-identical to those of
+// pfb_dada_unpack + row_fft_kernel.
+template <int N, class T, bool LOWCBF, bool PERM, bool GAIN>
+__global__ __launch_bounds__(NT) void row_fft_dada_kernel(RowFftArgs a, DadaRows d) {
+  constexpr int ROWS = RowShape<N>::ROWS;
+  extern __shared__ __attribute__((aligned(16))) float2 smem[];
+  const unsigned gs = 8u * (unsigned)d.share, g = blockIdx.x / gs, w = blockIdx.x % gs;
+  const int64_t slot = (int64_t)g * gs + (w & 7u) * (unsigned)d.share + (w >> 3);
+  const int64_t tile = slot / d.P;
+  const int pol = (int)(slot - tile * d.P);
+  if (tile >= d.tiles) return;  // uniform per workgroup
+  const int64_t r0 = tile * ROWS;
+  using Load = RowLoadDada<T, LOWCBF, PERM, GAIN>;
+  Load ld{static_cast<const typename Load::Pair*>(d.base), r0, a.n_rows - 1, d.t0, N, d.P, pol, a.perm, a.cgain};
+  RowStore st{a.out + pol * a.out_pol_stride, r0, a.n_rows, N, a.sds, a.remap, a.scale,
+              a.row_base, a.n_total, a.zs, a.nt};
+  row_fft_tile<N, +1>(ld, st, a.tw, smem);
 }
 
 // All passes of FFTPlan<N> after the first (one row, LDS -> ... -> `last`).

@@ -113,6 +113,28 @@ bool analysis_takes_offset(const AnalysisArgs& a);
 // the fused kernel reads a stream carry through `pre` with `pad` (non-streaming shapes)
 bool analysis_fused_takes_carry(const AnalysisArgs& a);
 
+// Complex-sample index of element (t, c, p) of a DADA data section of C channels and P
+// polarisations (NDIM 2): TFP order (reshape_dada_data.m:23-30) or the LowCBF heaps of 32
+// samples, [heap][chan][pol][sample] (reshape_low_cbf_data.m:31-41).  Shared by the unpack
+// kernels (pfb_layout.hip) and the channel IFFT's DADA row loader (pfb_common.hpp).
+template <bool LOWCBF>
+__host__ __device__ __forceinline__ int64_t dada_index(int64_t t, int c, int p, int C, int P) {
+  if constexpr (LOWCBF) return (((t >> 5) * C + c) * P + p) * 32 + (t & 31);
+  else return (t * C + c) * P + p;
+}
+
+// A DADA data section the channel IFFT reads in place (NBIT 8 / 16, NDIM 2; n_dat rows of the
+// plan's channels x polarisations): the launch's row 0 is file row t0.
+struct DadaIn {
+  const void* base;
+  int nbit, lowcbf;
+  int64_t n_dat, t0;
+};
+// Rows [t0, t0 + n_rows) of such a section -> out[pol][row][chan] complex float32 (the
+// pfb_dada_unpack kernels from a row offset: a LowCBF offset need not be a heap boundary)
+hipError_t launch_dada_unpack_rows(const DadaIn& d, int64_t n_rows, int C, int P, float2* out,
+                                   int64_t out_pol_stride, hipStream_t s);
+
 // Synthesis stage 1: per channelised time row, N-point inverse DFT across channels
 // (after the combine permutation and per-channel gain).  See DESIGN.md §synthesis.
 struct ChanIfftArgs {
@@ -127,7 +149,11 @@ struct ChanIfftArgs {
   const float* cgain;      // per-slot gain (null = 1)
   const float2* twN;
   int zblk = 1;            // Z rows in runs of zblk (1, 2, 4) per t0 (SynthBlockArgs::zblk)
+  // the rows come from a DADA section instead of `in` (chan_ifft_dada_supported; no perm / gain)
+  const DadaIn* dada = nullptr;
 };
+// the channel IFFT has a loader for DADA sections of this sample size (row_fft_dada_kernel)
+bool chan_ifft_dada_supported(int N, int nbit);
 
 // Synthesis stage 2: per block and group of t0, Nf-point FFT over time, kept-bin
 // selection with deripple gain and four-step twiddle, W-point inverse FFT,

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "pfb_api.h"
+#include "pfb_kernels.hpp"
 
 pfb_status pfb_set_error(pfb_status s, const char* msg);  // pfb_api.hip
 
@@ -67,23 +68,18 @@ __device__ __forceinline__ T to_sample(float v) {
 
 // ---------------------------------------------------------------- DADA unpack / pack
 // One thread per (t, c): reads the P (x NDIM) adjacent file samples of its (t, c) and
-// writes one complex sample into each polarisation's [t][chan] plane.
+// writes one complex sample into each polarisation's [t][chan] plane.  Output row 0 is file
+// row t0 (launch_dada_unpack_rows; 0 for pfb_dada_unpack).
 template <class T, int NDIM, bool LOWCBF>
 __global__ void __launch_bounds__(TPB) dada_unpack_kernel(const T* __restrict__ in, int64_t n_dat,
                                                           int C, int P, float2* __restrict__ out,
-                                                          int64_t ops) {
+                                                          int64_t ops, int64_t t0) {
   const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n_dat * C) return;
   const int64_t t = i / C;
   const int c = (int)(i - t * C);
   for (int p = 0; p < P; ++p) {
-    int64_t e;
-    if constexpr (LOWCBF) {
-      // heap of 32 samples: [heap][chan][pol][sample] (reshape_low_cbf_data.m:31-41)
-      e = (((t >> 5) * C + c) * P + p) * 32 + (t & 31);
-    } else {
-      e = (t * C + c) * P + p;  // reshape(data, n_pol, n_chan, []) of TFP
-    }
+    const int64_t e = pfb::dada_index<LOWCBF>(t0 + t, c, p, C, P);
     const float re = (float)in[e * NDIM];
     const float im = NDIM == 2 ? (float)in[e * NDIM + 1] : 0.f;
     out[p * ops + i] = make_float2(re, im);
@@ -149,9 +145,10 @@ __global__ void __launch_bounds__(TPB) dada_unpack_tfp4_kernel(const T* __restri
   }
 }
 
+// (t0: the first file row, LowCBF only — a TFP caller offsets `in` instead)
 template <class T>
 hipError_t launch_unpack(const void* in, int ndim, bool lowcbf, int64_t n_dat, int C, int P,
-                         float2* out, int64_t ops, hipStream_t s) {
+                         float2* out, int64_t ops, hipStream_t s, int64_t t0 = 0) {
   const unsigned g = blocks_for(n_dat * C);
   const T* src = static_cast<const T*>(in);
   const bool aligned = ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0) && (P == 1 || ops % 2 == 0);
@@ -164,14 +161,30 @@ hipError_t launch_unpack(const void* in, int ndim, bool lowcbf, int64_t n_dat, i
     return hipGetLastError();
   }
   if (ndim == 2) {
-    if (lowcbf) hipLaunchKernelGGL((dada_unpack_kernel<T, 2, true>), g, TPB, 0, s, src, n_dat, C, P, out, ops);
-    else hipLaunchKernelGGL((dada_unpack_kernel<T, 2, false>), g, TPB, 0, s, src, n_dat, C, P, out, ops);
+    if (lowcbf) hipLaunchKernelGGL((dada_unpack_kernel<T, 2, true>), g, TPB, 0, s, src, n_dat, C, P, out, ops, t0);
+    else hipLaunchKernelGGL((dada_unpack_kernel<T, 2, false>), g, TPB, 0, s, src, n_dat, C, P, out, ops, t0);
   } else {
-    if (lowcbf) hipLaunchKernelGGL((dada_unpack_kernel<T, 1, true>), g, TPB, 0, s, src, n_dat, C, P, out, ops);
-    else hipLaunchKernelGGL((dada_unpack_kernel<T, 1, false>), g, TPB, 0, s, src, n_dat, C, P, out, ops);
+    if (lowcbf) hipLaunchKernelGGL((dada_unpack_kernel<T, 1, true>), g, TPB, 0, s, src, n_dat, C, P, out, ops, t0);
+    else hipLaunchKernelGGL((dada_unpack_kernel<T, 1, false>), g, TPB, 0, s, src, n_dat, C, P, out, ops, t0);
   }
   return hipGetLastError();
 }
+
+}  // namespace
+
+hipError_t pfb::launch_dada_unpack_rows(const pfb::DadaIn& d, int64_t n_rows, int C, int P, float2* out,
+                                        int64_t ops, hipStream_t s) {
+  if (n_rows <= 0) return hipSuccess;
+  if ((d.nbit != 8 && d.nbit != 16) || d.t0 < 0 || d.t0 + n_rows > d.n_dat) return hipErrorInvalidValue;
+  // TFP rows are contiguous: the section from row t0 on is a section of its own
+  const int64_t skip = d.lowcbf ? 0 : d.t0 * C * P * 2 * (d.nbit / 8);
+  const void* in = static_cast<const char*>(d.base) + skip;
+  const int64_t t0 = d.lowcbf ? d.t0 : 0;
+  return d.nbit == 8 ? launch_unpack<int8_t>(in, 2, d.lowcbf != 0, n_rows, C, P, out, ops, s, t0)
+                     : launch_unpack<int16_t>(in, 2, d.lowcbf != 0, n_rows, C, P, out, ops, s, t0);
+}
+
+namespace {
 
 // ---------------------------------------------------------------- gather / transpose
 // out[o][t][j] = in[o][t][src(j)], src(j) = src0 + j + (j >= split ? shift : 0)

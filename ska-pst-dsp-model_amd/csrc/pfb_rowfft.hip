@@ -537,6 +537,52 @@ template hipError_t dispatch_row_fft<+1>(int, const RowFftArgs&, int, hipStream_
 
 bool chan_ifft_supported(int N) { return pow2_supported(N) || mixed_chan_supported(N); }
 
+// ----------------------------------------------------------------- DADA row loader
+// (N = 4096 keeps its pair / persistent kernels and their buffer-descriptor loads: staged)
+bool chan_ifft_dada_supported(int N, int nbit) {
+  return chan_ifft_supported(N) && N != 4096 && (nbit == 8 || nbit == 16);
+}
+
+template <int N, class T, bool LOWCBF>
+static hipError_t launch_row_fft_dada(const RowFftArgs& r, const DadaIn& in, int n_pol, hipStream_t s) {
+  constexpr int ROWS = RowShape<N>::ROWS;
+  const size_t bytes = ((size_t)ROWS * RowShape<N>::RS + tw_slots(N)) * sizeof(float2);
+  auto kern = row_fft_dada_kernel<N, T, LOWCBF, false, false>;
+  hipError_t e = set_lds(kern, bytes);
+  if (e != hipSuccess) return e;
+  const int64_t tiles = (r.n_rows + ROWS - 1) / ROWS;
+  // workgroups that share lines (DadaRows): the tile's polarisations, and in LowCBF order
+  // the (up to 4) tiles of one heap.  Measured at the C2 shape against blockIdx order
+  // (profiles/dada_synthesis_order_ab.jsonl): dual-pol TFP NBIT 16 0.210 vs 0.219 ms, LowCBF
+  // 0.101 vs 0.103 (one pol) and 0.246 vs 0.247; dual-pol TFP NBIT 8 was slower grouped
+  // (0.209 vs 0.197), so it keeps blockIdx order
+  int share = LOWCBF ? n_pol * (ROWS < 32 ? std::min(4, (32 + ROWS - 1) / ROWS) : 1) : sizeof(T) == 2 ? n_pol : 1;
+  if constexpr (kExperiments) {  // (PFB_DADA_SHARE=1: blockIdx order, A/B)
+    static const int forced = knob("PFB_DADA_SHARE") ? std::atoi(knob("PFB_DADA_SHARE")) : 0;
+    if (forced > 0) share = forced;
+  }
+  const int64_t gs = 8 * (int64_t)share;
+  const int64_t wgs = (tiles * n_pol + gs - 1) / gs * gs;
+  if (wgs > INT32_MAX) return hipErrorInvalidValue;
+  const DadaRows d{in.base, in.t0, tiles, n_pol, share};
+  return launch_kernel(kern, dim3((unsigned)wgs), dim3(NT), bytes, s, r, d);
+}
+
+template <class T, bool LOWCBF>
+static hipError_t dispatch_row_fft_dada(int N, const RowFftArgs& r, const DadaIn& in, int n_pol, hipStream_t s) {
+  switch (N) {
+#define PFB_DADA_N(n) \
+  case n: return launch_row_fft_dada<n, T, LOWCBF>(r, in, n_pol, s);
+    PFB_DADA_N(8) PFB_DADA_N(16) PFB_DADA_N(32) PFB_DADA_N(64) PFB_DADA_N(128) PFB_DADA_N(256)
+    PFB_DADA_N(512) PFB_DADA_N(1024) PFB_DADA_N(2048)
+    PFB_DADA_N(14) PFB_DADA_N(28) PFB_DADA_N(56) PFB_DADA_N(112) PFB_DADA_N(192) PFB_DADA_N(216)
+    PFB_DADA_N(224) PFB_DADA_N(384) PFB_DADA_N(432) PFB_DADA_N(448) PFB_DADA_N(768) PFB_DADA_N(864)
+    PFB_DADA_N(896) PFB_DADA_N(1536) PFB_DADA_N(1792) PFB_DADA_N(3072) PFB_DADA_N(3584)
+#undef PFB_DADA_N
+    default: return hipErrorInvalidValue;
+  }
+}
+
 hipError_t launch_chan_ifft(const ChanIfftArgs& c, hipStream_t s) {
   if (c.n_rows <= 0) return hipSuccess;
   // (the stage-1 rows are read by the synthesis right after: default store policy while they
@@ -550,6 +596,19 @@ hipError_t launch_chan_ifft(const ChanIfftArgs& c, hipStream_t s) {
   RowFftArgs r{c.in, c.in_pol_stride, c.out, c.out_pol_stride, c.n_rows, c.perm, c.cgain, c.twN,
                1.0f, 0, 0, 0, c.n_rows, c.zblk == 4 ? 2 : c.zblk == 2 ? 1 : 0, fits ? 0 : 1};
   if (c.zblk != 1 && c.zblk != 2 && c.zblk != 4) return hipErrorInvalidValue;
+  if (c.dada) {
+    const DadaIn& d = *c.dada;
+    // the loader has no permutation or gain instantiation, and reads whole complex samples
+    // of rows [t0, t0 + n_rows) of the section
+    if (c.perm || c.cgain || !chan_ifft_dada_supported(c.N, d.nbit) || d.t0 < 0 || d.t0 + c.n_rows > d.n_dat ||
+        (d.lowcbf && d.n_dat % 32) || reinterpret_cast<uintptr_t>(d.base) % (size_t)(d.nbit / 4))
+      return hipErrorInvalidValue;
+    if (d.nbit == 8)
+      return d.lowcbf ? dispatch_row_fft_dada<int8_t, true>(c.N, r, d, c.n_pol, s)
+                      : dispatch_row_fft_dada<int8_t, false>(c.N, r, d, c.n_pol, s);
+    return d.lowcbf ? dispatch_row_fft_dada<int16_t, true>(c.N, r, d, c.n_pol, s)
+                    : dispatch_row_fft_dada<int16_t, false>(c.N, r, d, c.n_pol, s);
+  }
   return dispatch_row_fft<+1>(c.N, r, c.n_pol, s);
 }
 

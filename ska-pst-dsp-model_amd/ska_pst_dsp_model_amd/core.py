@@ -413,6 +413,55 @@ class SynthesisPlan:
                 byref(n_out), mem, stream))
         return out[:, :n_out.value]
 
+    def execute_dada(self, raw, nbit: int, ndim: int = 2, lowcbf: bool = False, sample_offset: int = 1,
+                     stateful: bool = False, out=None):
+        """The synthesis of a DADA data section (``raw``: a device tensor of bytes or
+        samples, n_dat x n_chan x n_pol x ndim values of nbit in TFP or LowCBF order) —
+        bit for bit ``execute(layout.dada_unpack(raw, ...), layout="ptc")``, without the
+        unpacked samples crossing HBM where the channel IFFT can read the section itself
+        (pfb_synthesis_execute_dada / pfb_inverse_filterbank_execute_dada;
+        ``last_dada_input()`` tells).  n_dat is inferred as ``layout.dada_unpack`` does."""
+        t = _torch()
+        if not is_device_array(raw):
+            raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "execute_dada: expects a device tensor")
+        raw = raw.contiguous()
+        if int(nbit) not in (8, 16, 32, 64) or int(ndim) not in (1, 2):
+            n_dat = 0  # (the C ABI rejects the format)
+        else:
+            per = self.n_chan * self.n_pol * int(ndim) * (int(nbit) // 8)
+            n_dat = (raw.numel() * raw.element_size()) // per
+            if lowcbf:
+                n_dat -= n_dat % 32
+        if stateful:
+            cap = self.output_length(self.buffered_samples + n_dat)
+        else:
+            cap = self.output_length(max(n_dat - (int(sample_offset) - 1), 0))
+        if out is None:
+            out = t.empty((self.n_pol, max(cap, 0)), dtype=t.complex64, device=raw.device)
+        elif (out.dtype != t.complex64 or out.device != raw.device or not out.is_contiguous()
+              or out.dim() != 2 or out.shape[0] != self.n_pol):
+            raise ValueError(f"out must be a contiguous complex64 ({self.n_pol}, n) tensor on {raw.device}, "
+                             f"got {tuple(out.shape)} {out.dtype} {out.device}")
+        width = out.shape[1]
+        order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
+        src, dst, stream = c_void_p(raw.data_ptr()), c_void_p(out.data_ptr()), _stream_of(raw, self)
+        n_out = c_int64(0)
+        if stateful:
+            _lib.check(self._lib.pfb_inverse_filterbank_execute_dada(
+                self._h, src, int(nbit), int(ndim), order, n_dat, dst, width, width, byref(n_out), stream))
+        else:
+            _lib.check(self._lib.pfb_synthesis_execute_dada(
+                self._h, src, int(nbit), int(ndim), order, n_dat, int(sample_offset), dst, width, width,
+                byref(n_out), stream))
+        return out[:, :n_out.value]
+
+    def last_dada_input(self) -> str:
+        """How the plan's last DADA call read its section: 'fused' (the channel IFFT read
+        the file's own bytes), 'staged' (unpacked first), 'none' (no DADA call, or a cf32
+        call since) — pfb_synthesis_last_dada_input."""
+        m = int(self._lib.pfb_synthesis_last_dada_input(self._h))
+        return {_lib.PFB_DADA_INPUT_FUSED: "fused", _lib.PFB_DADA_INPUT_STAGED: "staged"}.get(m, "none")
+
 
 # ============================================================================ round trip
 def roundtrip(analysis: AnalysisPlan, synthesis: SynthesisPlan, x, sample_offset: int = 1,

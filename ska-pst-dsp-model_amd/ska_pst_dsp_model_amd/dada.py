@@ -23,7 +23,7 @@ import numpy as np
 
 from . import layout
 
-__all__ = ["read_header", "write_header", "read_dada_file", "write_dada_file",
+__all__ = ["read_header", "write_header", "read_dada_file", "read_dada_raw", "write_dada_file",
            "write_dada_header", "DADARead", "DADAWrite", "DADAFile", "add_fir_filter_to_header"]
 
 _NBIT_NP = {8: np.int8, 16: np.int16, 32: np.float32, 64: np.float64}
@@ -156,6 +156,17 @@ def read_dada_file(path, device=0):
     return _matlab_view(_unpack(_to_device_raw(raw, device), hdr, False)), hdr
 
 
+def read_dada_raw(path, device=0):
+    """The file's data section as it is: ``(raw, header)`` with ``raw`` a uint8 device
+    tensor of the section's bytes (for ``SynthesisPlan.execute_dada``, which reads them
+    without the unpacked copy ``read_dada_file`` makes)."""
+    with open(path, "rb") as f:
+        hdr = read_header(f)
+        f.seek(int(hdr["HDR_SIZE"]))
+        raw = np.fromfile(f, dtype=np.uint8)
+    return _to_device_raw(raw, device), hdr
+
+
 def write_dada_header(f, data_shape, nbit: int, hdr: dict, ndim: int = 2) -> dict:
     """write_dada_header.m:1-26 (NBIT from the data class, NDIM 2 for complex data,
     NPOL/NCHAN from the Matlab (n_pol, n_chan, n_dat) shape)."""
@@ -223,6 +234,15 @@ class DADARead:
         raw = np.fromfile(self._f, dtype=np.uint8, count=nbytes)
         dev = _to_device_raw(raw, self.device)
         return self, _matlab_view(_unpack(dev, self.header, self.low_cbf_input))
+
+    def generate_raw(self, nsample: int):
+        """The next nsample rows' bytes as a uint8 device tensor, not unpacked (for
+        ``InverseFilterBank.execute_dada``).  LowCBF files are read in whole heaps."""
+        if self.low_cbf_input and nsample % 32:
+            raise ValueError("generate_raw: LowCBF data are heaps of 32 samples")
+        nbytes = nsample * self.n_chan * self.n_pol * self.n_dim * (self.n_bit // 8)
+        raw = np.fromfile(self._f, dtype=np.uint8, count=nbytes)
+        return self, _to_device_raw(raw, self.device)
 
     def close(self):
         if self._f:

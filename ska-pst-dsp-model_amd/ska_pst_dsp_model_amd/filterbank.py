@@ -200,6 +200,17 @@ class InverseFilterBank(DeChannelizer):
         out = plan.execute(input, stateful=True)
         return self, out[:, None, :]
 
+    def execute_dada(self, raw, nbit: int, ndim: int = 2, lowcbf: bool = False, n_pol: int = 1):
+        """``execute`` of the next chunk as the file holds it: ``raw`` is a device tensor of
+        the DADA section's bytes (``DADARead.generate_raw``), ``nchan`` channels x ``n_pol``
+        polarisations.  Same output and carry as ``execute(DADARead.generate(...))``."""
+        if int(self.sample_offset) < 0:
+            raise ValueError("sample_offset is 0-based (>= 0)")
+        plan = self._ensure_plan(int(n_pol), int(self.nchan))
+        plan.set_stream_sample_offset(int(self.sample_offset))
+        out = plan.execute_dada(raw, nbit, ndim=ndim, lowcbf=lowcbf, stateful=True)
+        return self, out[:, None, :]
+
     def reset(self):
         if self._plan is not None:
             self._plan.reset()

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import dada
 from .config import as_rational
-from .core import polyphase_analysis, polyphase_analysis_padded, polyphase_synthesis
+from .core import polyphase_analysis, polyphase_analysis_padded, synthesis_plan
 from .firio import read_fir_filter_coeff
 from .window import PFBWindow
 
@@ -94,7 +94,10 @@ def synthesize(input_data_file_path, input_fft_length: int = None, input_overlap
     nf, ov = int(input_fft_length), int(input_overlap)
     output_base = f"synthesize.{nf}"
     _, _, output_file_name = create_output_file_names(output_file_name, output_base)
-    data, hdr = dada.read_dada_file(input_data_file_path, device)
+    raw, hdr = dada.read_dada_raw(input_data_file_path, device)
+    if hdr.get("INSTRUMENT") == "LowCBF":
+        raise ValueError("synthesize: LowCBF files are read with DADARead "
+                         "(read_dada_file.m has no heap reordering)")
     channels = int(hdr["NCHAN"])
     os_factor = as_rational(hdr["OS_FACTOR"])
     taps = np.array([float(v) for v in hdr["COEFF_0"].split(",")])
@@ -102,9 +105,11 @@ def synthesize(input_data_file_path, input_fft_length: int = None, input_overlap
     sh = dict(hdr)
     tsamp = float(hdr.get("TSAMP", "1"))
     sh["TSAMP"] = _num2str(tsamp / (os_factor.de / os_factor.nu) / channels)
-    out = polyphase_synthesis(data, 1, nf, os_factor,
-                              {"apply_deripple": int(bool(deripple)), "filter_coeff": taps}, 1,
-                              ov, taper)
+    # polyphase_synthesis(data, 1, nf, os_factor, deripple, 1, ov, taper) of the file's
+    # samples, read by the synthesis from the section's own bytes (no unpacked copy)
+    plan = synthesis_plan(channels, os_factor, nf, ov, True, 1, bool(deripple), taps, taper, None,
+                          int(hdr["NPOL"]), raw.device.index or 0)
+    out = plan.execute_dada(raw, int(hdr["NBIT"]), ndim=int(hdr["NDIM"]))[:, None, :]
     path = os.path.join(output_dir, output_file_name)
     dada.write_dada_file(path, out, sh)
     return dada.DADAFile(path, device).load_data()
