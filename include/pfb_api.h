@@ -369,6 +369,52 @@ pfb_status pfb_inverse_filterbank_execute_dada(pfb_synthesis_plan* plan, const v
                                                int64_t out_capacity, int64_t* n_out, void* stream);
 int32_t pfb_synthesis_last_dada_input(const pfb_synthesis_plan* plan);
 
+/* The synthesis calls reading their channelised rows strided (device memory only): channel c
+ * of row t of polarisation p is in[p * in_pol_stride + t * in_row_stride + c * in_chan_stride]
+ * — the input-side mirror of pfb_filterbank_execute_strided.  Polarisations may interleave
+ * inside a row: the per-coarse-channel slices of TwoStageInverseFilterBank.m:124-126 are
+ * in_pol_stride = nch_in, in_row_stride = nchan, in_chan_stride = 1 over the assembled
+ * two-stage product, with no gather.  Rows may be channel-major (in_row_stride = 1,
+ * in_chan_stride = series length), or a channel window of a wider product.  The input is only
+ * read, so polarisations may overlap.
+ * The output, *n_out, the status codes, pfb_inverse_filterbank_buffered and the stream state
+ * are those of pfb_synthesis_execute / pfb_inverse_filterbank_execute on a packed
+ * [pol][t][chan] copy of the same elements, bit for bit: the channel IFFT sees the same
+ * values in the same butterflies.  No element outside the mapped ones is loaded.
+ * Checks, all before any launch or change of the stream state (a rejected stream call leaves
+ * the carry and the buffered count untouched): a stride <= 0, or in_capacity (the pfb_cf32
+ * elements available from `in`) not beyond the furthest element read, (n_pol-1) in_pol_stride
+ * + (rows-1) in_row_stride + (n_chan-1) in_chan_stride, is PFB_ERR_INVALID_ARG, as are the
+ * null, sample_offset and output-stride conditions of the packed calls; an output capacity
+ * below the output length is PFB_ERR_BUFFER_TOO_SMALL.
+ * IN_PLACE: the channel IFFT's first pass loads through the layout (64-bit addresses, plain
+ * loads) and the packed copy never exists — every channel count below 4096, with or without
+ * the combine permutation, of a plan without temporal-taper gain or spectral taper.  A
+ * stream call reads the blocks made of new rows only in place; the blocks that start in the
+ * carry are stitched from the packed cf32 carry and the head of the new rows, and the new
+ * carry is their tail, both copied out of the layout.  STAGED: any other plan (4096
+ * channels, a Hann temporal taper, a spectral taper) has the rows copied through the layout
+ * into a plan-owned packed buffer by one launch and runs the packed path, so these calls
+ * accept every plan the packed ones accept.  pfb_synthesis_last_strided_input: which of the
+ * two the plan's last strided call took (IN_PLACE when any of its channel IFFTs read through
+ * the layout), NONE before one or after a packed or DADA call, -1 for a null plan. */
+typedef enum pfb_strided_input {
+  PFB_STRIDED_INPUT_NONE = 0,
+  PFB_STRIDED_INPUT_IN_PLACE = 1,
+  PFB_STRIDED_INPUT_STAGED = 2
+} pfb_strided_input;
+pfb_status pfb_synthesis_execute_strided(pfb_synthesis_plan* plan, const pfb_cf32* in,
+                                         int64_t in_pol_stride, int64_t in_row_stride,
+                                         int64_t in_chan_stride, int64_t in_capacity, int64_t n_dat,
+                                         int64_t sample_offset, pfb_cf32* out, int64_t out_pol_stride,
+                                         int64_t out_capacity, int64_t* n_out, void* stream);
+pfb_status pfb_inverse_filterbank_execute_strided(pfb_synthesis_plan* plan, const pfb_cf32* in,
+                                                  int64_t in_pol_stride, int64_t in_row_stride,
+                                                  int64_t in_chan_stride, int64_t in_capacity,
+                                                  int64_t n_in, pfb_cf32* out, int64_t out_pol_stride,
+                                                  int64_t out_capacity, int64_t* n_out, void* stream);
+int32_t pfb_synthesis_last_strided_input(const pfb_synthesis_plan* plan);
+
 /* [pol][t][chan] complex float32 -> DADA TFP data section (NDIM 2) of NBIT 8/16/32/64;
  * integer types follow Matlab's cast (round half away from zero, saturate).  Replaces
  * write_dada_data.m:32-50 (data written with the class write_dada_header.m:13-22

@@ -8,6 +8,8 @@ one MI355X, as algorithmic HBM bytes / time against the 8 TB/s peak.
   * two-stage analysis cascade (256 x 256 ch; stage 2 batched over 256 series)
   * --only-dada: synthesis from a DADA section at the C2 shape, the staged pair
     (pfb_dada_unpack + pfb_synthesis_execute) against pfb_synthesis_execute_dada, interleaved
+  * --only-twostage-inverse: TwoStageInverseFilterBank with the channel gather against the
+    strided input (pfb_inverse_filterbank_execute_strided), interleaved
 
 Prints one JSON object per line.  Usage: python scripts/bench_aux.py [--reps N]
 """
@@ -51,7 +53,10 @@ def main():
     ap.add_argument("--only-twostage", action="store_true")
     ap.add_argument("--only-dada", action="store_true",
                     help="the dada_synthesis A/B alone (--reps: calls per timed window)")
-    ap.add_argument("--rounds", type=int, default=15, help="--only-dada: interleaved A/B windows per case")
+    ap.add_argument("--only-twostage-inverse", action="store_true",
+                    help="the inverse cascade's gather vs strided-input A/B alone (--reps: calls per window)")
+    ap.add_argument("--rounds", type=int, default=15,
+                    help="--only-dada / --only-twostage-inverse: interleaved A/B windows per case")
     ap.add_argument("--padded-cascade", default="default",
                     choices=["default", "strided", "no-stage1", "no-stage2", "gather"],
                     help="the SKA-Mid padded cascade's stores: the library default; both stages strided; "
@@ -83,6 +88,8 @@ def main():
         return twostage(torch, pfb, noise, args.reps, args.padded_cascade)
     if args.only_dada:
         return dada_synthesis(torch, pfb, dev, max(args.reps, 20), args.rounds)
+    if args.only_twostage_inverse:
+        return twostage_inverse(torch, pfb, noise, max(args.reps, 20), max(args.rounds, 5))
     # ---- C2' (4/3) round trip
     taps43 = pfb.design_PFB_FIR_filter(256, "4/3", 12)
     n = 1 << 24
@@ -244,6 +251,59 @@ def dada_synthesis(torch, pfb, dev, reps, rounds):
                 "B_first_pass_bytes_per_sample": 2 * nbit // 8,
                 "samples": samples}), flush=True)
         del syn, out_a, out_b, x
+
+
+def twostage_inverse(torch, pfb, noise, reps, rounds):
+    """TwoStageInverseFilterBank stream calls, the gather against the strided input.  Shapes:
+    the inverse of BASELINE configs[2]'s cascade (4096 coarse x 14 fine channels, critical,
+    stage-2 bank 16 ch 8/7, Nf 128, Ov 16; 1170 rows = one 2^26-sample-equivalent call) and the
+    256 x 256 oversampled cascade (stage-2 bank 256 ch 8/7, Nf 256, Ov 48; 1024 rows).
+    A: strided_input = False (pfb_gather_channels + the packed call).  B: strided_input = True
+    (pfb_inverse_filterbank_execute_strided).  Two objects fed the same calls, so their carries
+    agree; the outputs of the first calls are asserted equal; then `rounds` windows of `reps`
+    calls of each side, alternating A and B in one process, after a warm-up of both.  One line
+    per shape with every window's per-call time and each side's median, min and max."""
+    def cfg(n, nf, ov):
+        return dict(filt_coeff=pfb.design_PFB_FIR_filter(n, "8/7", 10 if n == 16 else 12), channels=n,
+                    os_factor="8/7", input_fft_length=nf, input_overlap=ov, deripple=False,
+                    temporal_taper="tukey")
+    shapes = [("SKA-Mid inverse 4096x14 critical", cfg(16, 128, 16), 14, 4096, 1170),
+              ("256x256 oversampled", cfg(256, 256, 48), 256, 256, 1024)]
+    for name, c, nch2, n_coarse, rows in shapes:
+        x = noise(1, rows, n_coarse * nch2).transpose(1, 2)      # (1, nchan, T), channel fastest
+        sides = []
+        for strided in (False, True):
+            ti = pfb.TwoStageInverseFilterBank(c)
+            ti.nch2 = nch2
+            ti.strided_input = strided
+            sides.append(ti)
+        a_obj, b_obj = sides
+        for _ in range(3):
+            _, oa = a_obj.execute(x)
+            _, ob = b_obj.execute(x)
+            torch.cuda.synchronize()
+            assert oa.shape == ob.shape and oa.shape[2] > 0 and torch.equal(oa, ob), f"{name}: outputs differ"
+        path = b_obj.stage2._plan.last_strided_input()
+        side_a, side_b = (lambda: a_obj.execute(x)), (lambda: b_obj.execute(x))
+        for _ in range(2):
+            timeit(torch, side_a, reps)
+            timeit(torch, side_b, reps)
+        ta, tb = [], []
+        for _ in range(rounds):
+            ta.append(timeit(torch, side_a, reps))
+            tb.append(timeit(torch, side_b, reps))
+        med_a, med_b = float(np.median(ta)), float(np.median(tb))
+        print(json.dumps({
+            "kernel": "twostage_inverse", "shape": name, "rows": rows, "n_coarse": n_coarse, "nch_in": nch2,
+            "path": path, "calls_per_window": reps, "windows": rounds, "outputs_equal": True,
+            "A_gather_ms": [round(t, 4) for t in ta], "B_strided_ms": [round(t, 4) for t in tb],
+            "A_median_ms": round(med_a, 4), "B_median_ms": round(med_b, 4),
+            "A_spread_ms": round(max(ta) - min(ta), 4), "B_spread_ms": round(max(tb) - min(tb), 4),
+            "B_below_A_by_ms": round(med_a - med_b, 4),
+            "grid_order": os.environ.get("PFB_STRIDED_SHARE", "default"),
+            "samples": rows * n_coarse * nch2}), flush=True)
+        del x, a_obj, b_obj, sides, oa, ob
+        torch.cuda.empty_cache()
 
 
 def cpu_baselines(pfb):

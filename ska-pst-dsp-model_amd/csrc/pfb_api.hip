@@ -898,6 +898,7 @@ struct pfb_synthesis_plan {
   int stage1 = PFB_STAGE1_AUTO;  // pfb_synthesis_set_stage1_rows
   int last_stage1 = 0;           // pfb_synthesis_last_stage1_rows: where the last launch got its rows
   int last_dada = PFB_DADA_INPUT_NONE;  // pfb_synthesis_last_dada_input
+  int last_strided = PFB_STRIDED_INPUT_NONE;  // pfb_synthesis_last_strided_input
   int rt_chunk_blocks = 64;  // round-trip pipeline chunk (PFB_RT_CHUNK_BLOCKS)
   int timing_mask = 0;  // PFB_TIMING_MASK (timing experiments; results invalid when set)
   int ranges = -1;  // PFB_SYNTH_RANGES: 0 one workgroup per block, -1 persistent auto, >0 persistent
@@ -1017,12 +1018,13 @@ static pfb_status synthesis_spectral(pfb_synthesis_plan* p, const float2* in, in
 // negative row_shift: block 0 starts -row_shift rows into `in` (InverseFilterBank's
 // sample_offset applied to the concatenated rows))
 // (dada: the call's rows are a DADA section read in place, `in` is unused — the section's
-// row 0 is the call's row row_shift)
+// row 0 is the call's row row_shift; strided: the same for rows behind a strided layout)
 static pfb_status synthesis_chunk(pfb_synthesis_plan* p, const float2* in, int64_t in_ps, int64_t b0,
                                   int64_t nb, float2* out, int64_t out_ps, int64_t out_limit,
-                                  hipStream_t s, int64_t row_shift = 0, const pfb::DadaIn* dada = nullptr) {
+                                  hipStream_t s, int64_t row_shift = 0, const pfb::DadaIn* dada = nullptr,
+                                  const pfb::StridedIn* strided = nullptr) {
   if (p->has_spectral) {
-    if (dada) return fail(PFB_ERR_UNSUPPORTED, "DADA rows with a spectral taper");
+    if (dada || strided) return fail(PFB_ERR_UNSUPPORTED, "rows read in place with a spectral taper");
     // (a negative row shift: the blocks start -row_shift rows into `in` — a sample offset)
     if (row_shift > 0) return fail(PFB_ERR_UNSUPPORTED, "row shift with a spectral taper");
     return synthesis_spectral(p, in + (-row_shift) * p->N, in_ps, b0, nb, out, out_ps, out_limit, s);
@@ -1033,12 +1035,19 @@ static pfb_status synthesis_chunk(pfb_synthesis_plan* p, const float2* in, int64
   float2* Z = p->Z.as<float2>();
   pfb::ChanIfftArgs c{};
   pfb::DadaIn dd{};
+  pfb::StridedIn sd{};
   if (dada) {
     dd = *dada;
     dd.t0 = b0 * p->keep - row_shift;
     if (dd.t0 < 0 || dd.t0 + rows > dd.n_dat) return fail(PFB_ERR_INVALID_ARG, "rows outside the DADA section");
     c.dada = &dd;
     p->last_dada = PFB_DADA_INPUT_FUSED;
+  } else if (strided) {
+    sd = *strided;
+    sd.t0 = b0 * p->keep - row_shift;
+    if (sd.t0 < 0 || sd.t0 + rows > sd.n_dat) return fail(PFB_ERR_INVALID_ARG, "rows outside the strided input");
+    c.strided = &sd;
+    p->last_strided = PFB_STRIDED_INPUT_IN_PLACE;
   } else {
     c.in = in + (b0 * p->keep - row_shift) * p->N;
   }
@@ -1138,12 +1147,13 @@ static int64_t synthesis_chunk_blocks(const pfb_synthesis_plan* p, int64_t B) {
 // blocks [b_lo, b_hi) in chunks (see synthesis_chunk for row_shift)
 static pfb_status synthesis_range(pfb_synthesis_plan* p, const float2* in, int64_t in_ps, int64_t b_lo,
                                   int64_t b_hi, float2* out, int64_t out_ps, int64_t out_limit,
-                                  hipStream_t s, int64_t row_shift = 0, const pfb::DadaIn* dada = nullptr) {
+                                  hipStream_t s, int64_t row_shift = 0, const pfb::DadaIn* dada = nullptr,
+                                  const pfb::StridedIn* strided = nullptr) {
   if (b_hi <= b_lo) return PFB_OK;
   const int64_t CB = synthesis_chunk_blocks(p, b_hi - b_lo);
   for (int64_t b0 = b_lo; b0 < b_hi; b0 += CB) {
     pfb_status st = synthesis_chunk(p, in, in_ps, b0, std::min<int64_t>(CB, b_hi - b0), out, out_ps,
-                                    out_limit, s, row_shift, dada);
+                                    out_limit, s, row_shift, dada, strided);
     if (st != PFB_OK) return st;
   }
   return PFB_OK;
@@ -1511,17 +1521,55 @@ static pfb_status dada_stage(pfb_synthesis_plan* p, const DadaSection& sec, int6
                          reinterpret_cast<pfb_cf32*>(p->stage_in.p), rows * p->N, s);
 }
 
-// pfb_synthesis_execute; sec: the rows are a DADA section (device memory) instead of `in`
+// The layout of a strided cf32 input (pfb_synthesis_execute_strided,
+// pfb_inverse_filterbank_execute_strided): element (pol, row, chan) at in[pol ps + row rs +
+// chan cs], `cap` elements available from `in`
+struct StridedView {
+  int64_t ps, rs, cs, cap;
+};
+
+// every stride positive and the furthest element read inside the capacity (pfb_api.h)
+static pfb_status strided_view_check(const pfb_synthesis_plan* p, const StridedView& v, int64_t rows) {
+  if (v.ps <= 0 || v.rs <= 0 || v.cs <= 0) return fail(PFB_ERR_INVALID_ARG, "input strides must be positive");
+  if (rows <= 0) return PFB_OK;
+  const __int128 far = (__int128)(p->n_pol - 1) * v.ps + (__int128)(rows - 1) * v.rs + (__int128)(p->N - 1) * v.cs;
+  if (far >= (__int128)v.cap)
+    return fail(PFB_ERR_INVALID_ARG, "in_capacity %lld does not cover the furthest element read",
+                (long long)v.cap);
+  return PFB_OK;
+}
+
+// the channel IFFT can read the rows through the layout (pfb_api.h, IN_PLACE)
+static bool strided_in_place(const pfb_synthesis_plan* p) {
+  return pfb::chan_ifft_strided_supported(p->N) && !p->has_cgain && !p->has_spectral;
+}
+
+// STAGED: `rows` rows copied through the layout into the plan's staging buffer
+// ([pol][row][chan], pol stride rows N)
+static pfb_status strided_stage(pfb_synthesis_plan* p, const pfb::StridedIn& d, int64_t rows, hipStream_t s) {
+  HIPCHK(p->stage_in.ensure((size_t)p->n_pol * std::max<int64_t>(rows, 1) * p->N * sizeof(float2)));
+  p->last_strided = PFB_STRIDED_INPUT_STAGED;
+  HIPCHK(pfb::launch_strided_rows_copy(d, rows, p->N, p->n_pol, p->stage_in.as<float2>(), rows * p->N, s));
+  return PFB_OK;
+}
+
+// pfb_synthesis_execute; sec: the rows are a DADA section (device memory) instead of `in`;
+// sv: `in` is read through a strided layout (device memory)
 static pfb_status synthesis_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
                                  const DadaSection* sec, int64_t n_dat, int64_t sample_offset,
                                  pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
-                                 int32_t mem, void* stream) {
+                                 int32_t mem, void* stream, const StridedView* sv = nullptr) {
   if (sec) in = static_cast<const pfb_cf32*>(sec->base);
   if (!p || (!in && n_dat > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
   if (sample_offset < 1) return fail(PFB_ERR_INVALID_ARG, "sample_offset is 1-based (>= 1)");
   if (n_dat < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_dat");
+  if (sv) {
+    const pfb_status st = strided_view_check(p, *sv, n_dat);
+    if (st != PFB_OK) return st;
+  }
   HIPCHK(hipSetDevice(p->device));
   p->last_dada = PFB_DADA_INPUT_NONE;
+  p->last_strided = PFB_STRIDED_INPUT_NONE;
   hipStream_t s = (hipStream_t)stream;
   const int64_t off = std::min<int64_t>(sample_offset - 1, std::max<int64_t>(n_dat, 0));
   const int64_t n = n_dat - off;  // in = in(:, :, sample_offset:end)  (:99)
@@ -1532,8 +1580,19 @@ static pfb_status synthesis_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int6
   if (cap < olen) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld",
                               (long long)cap, (long long)olen);
   if (mem == PFB_MEM_DEVICE) {
-    if ((!sec && in_ps < n_dat * p->N) || out_ps < olen)
+    if ((!sec && !sv && in_ps < n_dat * p->N) || out_ps < olen)
       return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
+    if (sv) {
+      const pfb::StridedIn d{(const float2*)in, sv->ps, sv->rs, sv->cs, n_dat, 0};
+      if (strided_in_place(p))
+        // the blocks start `off` rows into the layout (a negative row shift)
+        return synthesis_range(p, nullptr, 0, 0, synth_blocks(p, n), (float2*)out, out_ps, olen, s, -off, nullptr,
+                               &d);
+      const pfb_status st = strided_stage(p, d, n_dat, s);
+      if (st != PFB_OK) return st;
+      in = reinterpret_cast<const pfb_cf32*>(p->stage_in.p);
+      in_ps = n_dat * p->N;
+    }
     if (sec) {
       if (dada_fusable(p, *sec)) {
         // the blocks start `off` rows into the section (a negative row shift)
@@ -1579,6 +1638,17 @@ pfb_status pfb_synthesis_execute_dada(pfb_synthesis_plan* p, const void* in, int
 
 int32_t pfb_synthesis_last_dada_input(const pfb_synthesis_plan* p) { return p ? p->last_dada : -1; }
 
+pfb_status pfb_synthesis_execute_strided(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
+                                         int64_t in_rs, int64_t in_cs, int64_t in_cap, int64_t n_dat,
+                                         int64_t sample_offset, pfb_cf32* out, int64_t out_ps, int64_t cap,
+                                         int64_t* n_out, void* stream) {
+  const StridedView sv{in_ps, in_rs, in_cs, in_cap};
+  return synthesis_exec(p, in, in_ps, nullptr, n_dat, sample_offset, out, out_ps, cap, n_out, PFB_MEM_DEVICE,
+                        stream, &sv);
+}
+
+int32_t pfb_synthesis_last_strided_input(const pfb_synthesis_plan* p) { return p ? p->last_strided : -1; }
+
 pfb_status pfb_inverse_filterbank_set_sample_offset(pfb_synthesis_plan* p, int64_t sample_offset) {
   if (!p) return fail(PFB_ERR_INVALID_ARG, "null plan");
   if (sample_offset < 0) return fail(PFB_ERR_INVALID_ARG, "sample_offset is 0-based (>= 0)");
@@ -1595,14 +1665,23 @@ pfb_status pfb_inverse_filterbank_set_sample_offset(pfb_synthesis_plan* p, int64
 // blocks of new rows read it in place, and whatever the cf32 call copies out of `in` — the
 // stitched head, the carry — is unpacked from the section's rows instead.  Otherwise the
 // section is unpacked whole once every check has passed, and the cf32 path runs.)
+// (sv: the new rows lie behind a strided layout in device memory.  The same split: the
+// blocks of new rows read through the layout where the channel IFFT can, the stitched head
+// and the carry are copied out of it by the strided-rows copy kernel; otherwise the rows are
+// copied whole once every check has passed, and the cf32 path runs.)
 static pfb_status ifb_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps, const DadaSection* sec,
                            int64_t n_in, pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
-                           int32_t mem, void* stream) {
+                           int32_t mem, void* stream, const StridedView* sv = nullptr) {
   if (sec) in = static_cast<const pfb_cf32*>(sec->base);
   if (!p || (!in && n_in > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
   if (n_in < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_in");
+  if (sv) {
+    const pfb_status st = strided_view_check(p, *sv, n_in);
+    if (st != PFB_OK) return st;
+  }
   HIPCHK(hipSetDevice(p->device));
   p->last_dada = PFB_DADA_INPUT_NONE;
+  p->last_strided = PFB_STRIDED_INPUT_NONE;
   hipStream_t s = (hipStream_t)stream;
   const int N = p->N;
   const int64_t total = p->buffered + n_in;
@@ -1632,11 +1711,25 @@ static pfb_status ifb_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in
   if (n_out) *n_out = olen;
   if (olen > cap) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld",
                               (long long)cap, (long long)olen);
-  if (mem == PFB_MEM_DEVICE && ((!sec && in_ps < n_in * N) || out_ps < olen))
+  if (mem == PFB_MEM_DEVICE && ((!sec && !sv && in_ps < n_in * N) || out_ps < olen))
     return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
   if (olen > 0 && !out) return fail(PFB_ERR_INVALID_ARG, "null output");
   pfb::DadaIn dd{};
   const pfb::DadaIn* dada = nullptr;
+  pfb::StridedIn sd{};
+  const pfb::StridedIn* strided = nullptr;
+  if (sv) {
+    sd = pfb::StridedIn{(const float2*)in, sv->ps, sv->rs, sv->cs, n_in, 0};
+    if (strided_in_place(p)) {
+      strided = &sd;
+      in = nullptr;
+    } else {
+      const pfb_status st = strided_stage(p, sd, n_in, s);
+      if (st != PFB_OK) return st;
+      in = reinterpret_cast<const pfb_cf32*>(p->stage_in.p);
+      in_ps = n_in * N;
+    }
+  }
   if (sec) {
     if (dada_fusable(p, *sec)) {
       dd = pfb::DadaIn{sec->base, sec->nbit, sec->order == PFB_DADA_LOWCBF, n_in, 0};
@@ -1656,6 +1749,12 @@ static pfb_status ifb_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in
       d.t0 = row0;
       if (p->last_dada == PFB_DADA_INPUT_NONE) p->last_dada = PFB_DADA_INPUT_STAGED;
       return pfb::launch_dada_unpack_rows(d, n, N, p->n_pol, dst, dps, s);
+    }
+    if (strided) {
+      pfb::StridedIn d = sd;
+      d.t0 = row0;
+      if (p->last_strided == PFB_STRIDED_INPUT_NONE) p->last_strided = PFB_STRIDED_INPUT_STAGED;
+      return pfb::launch_strided_rows_copy(d, n, N, p->n_pol, dst, dps, s);
     }
     return copy_pols(dst, dps, (const float2*)in + row0 * N, in_ps, n * N, p->n_pol, kin, s);
   };
@@ -1680,7 +1779,7 @@ static pfb_status ifb_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in
           if (st != PFB_OK) return st;
         }
         pfb_status st = synthesis_range(p, (const float2*)in, in_ps, b_s, B, (float2*)out, out_ps, olen, s,
-                                        Bc - so, dada);
+                                        Bc - so, dada, strided);
         if (st != PFB_OK) return st;
       }
       if (buffered > 0) {
@@ -1697,10 +1796,11 @@ static pfb_status ifb_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in
   if (p->buffered == 0 && mem == PFB_MEM_DEVICE) {
     w = (const float2*)in;
     wps = in_ps;
-    if (dada) {
-      // nothing carried: every block reads the section in place, the carry is its unpacked tail
+    if (dada || strided) {
+      // nothing carried: every block reads the section (the layout) in place, the carry is
+      // its unpacked (copied) tail
       if (olen > 0) {
-        pfb_status st = synthesis_range(p, nullptr, 0, 0, B, (float2*)out, out_ps, olen, s, -so, dada);
+        pfb_status st = synthesis_range(p, nullptr, 0, 0, B, (float2*)out, out_ps, olen, s, -so, dada, strided);
         if (st != PFB_OK) return st;
       }
       if (buffered > 0) {
@@ -1754,6 +1854,14 @@ pfb_status pfb_inverse_filterbank_execute_dada(pfb_synthesis_plan* p, const void
   const pfb_status st = dada_section_check(p, sec, n_in);
   if (st != PFB_OK) return st;
   return ifb_exec(p, nullptr, 0, &sec, n_in, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream);
+}
+
+pfb_status pfb_inverse_filterbank_execute_strided(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
+                                                  int64_t in_rs, int64_t in_cs, int64_t in_cap, int64_t n_in,
+                                                  pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
+                                                  void* stream) {
+  const StridedView sv{in_ps, in_rs, in_cs, in_cap};
+  return ifb_exec(p, in, in_ps, nullptr, n_in, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream, &sv);
 }
 
 int64_t pfb_inverse_filterbank_buffered(const pfb_synthesis_plan* p) { return p ? p->buffered : -1; }

@@ -313,6 +313,24 @@ struct RowLoadDada {
   }
 };
 
+// RowLoad's strided twin (StridedIn): element (row, i) at in + (t0 + row) rs + c cs, `in`
+// already offset to the polarisation.  64-bit addresses and plain loads (lines shared by
+// neighbouring polarisations or rows stay cacheable); the same clamp, so no element outside
+// rows [t0, t0 + last] x the N mapped channels is loaded.  The values are the ones a packed
+// copy would hold for RowLoad.
+template <bool PERM>
+struct RowLoadStrided {
+  static constexpr bool kIsLds = false;
+  const float2* in;
+  int64_t r0, last, t0, rs, cs;
+  const int* perm;
+  __device__ __forceinline__ float2 load(int row, int i) const {
+    const int64_t r = min(r0 + row, last);
+    const int c = PERM ? perm[i] : i;
+    return in[(t0 + r) * rs + c * cs];
+  }
+};
+
 struct RowStore {
   static constexpr bool kIsLds = false;
   float2* out;
@@ -470,6 +488,43 @@ __global__ __launch_bounds__(NT) void row_fft_dada_kernel(RowFftArgs a, DadaRows
   const int64_t r0 = tile * ROWS;
   using Load = RowLoadDada<T, LOWCBF, PERM, GAIN>;
   Load ld{static_cast<const typename Load::Pair*>(d.base), r0, a.n_rows - 1, d.t0, N, d.P, pol, a.perm, a.cgain};
+  RowStore st{a.out + pol * a.out_pol_stride, r0, a.n_rows, N, a.sds, a.remap, a.scale,
+              a.row_base, a.n_total, a.zs, a.nt};
+  row_fft_tile<N, +1>(ld, st, a.tw, smem);
+}
+
+// Workgroup -> (tile, pol) of row_fft_strided_kernel.  share = 0 (every release launch):
+// blockIdx.x = tile, blockIdx.y = pol, row_fft_kernel's grid.  share > 0 (experiments builds,
+// pfb_rowfft.hip): a 1-D grid in DadaRows' order — `share` consecutive polarisations of one
+// tile are consecutive workgroups of ONE XCD — meant for polarisations closer together than a
+// 128-B line (the inverse cascade's 112-B slices of one row); it measured slower there.
+struct StridedRows {
+  StridedIn in;
+  int64_t tiles;
+  int P, share;
+};
+
+// row_fft_kernel<N, +1, PERM, false> with the rows read through a strided layout
+// (RowLoadStrided): same passes, tables and RowStore, so the Z rows are bit-identical to
+// those row_fft_kernel makes from a packed copy.
+template <int N, bool PERM>
+__global__ __launch_bounds__(NT) void row_fft_strided_kernel(RowFftArgs a, StridedRows d) {
+  constexpr int ROWS = RowShape<N>::ROWS;
+  extern __shared__ __attribute__((aligned(16))) float2 smem[];
+  int64_t tile;
+  int pol;
+  if (d.share > 0) {
+    const unsigned gs = 8u * (unsigned)d.share, g = blockIdx.x / gs, w = blockIdx.x % gs;
+    const int64_t slot = (int64_t)g * gs + (w & 7u) * (unsigned)d.share + (w >> 3);
+    tile = slot / d.P;
+    pol = (int)(slot - tile * d.P);
+    if (tile >= d.tiles) return;  // uniform per workgroup
+  } else {
+    tile = blockIdx.x;
+    pol = blockIdx.y;
+  }
+  const int64_t r0 = tile * ROWS;
+  RowLoadStrided<PERM> ld{d.in.base + pol * d.in.ps, r0, a.n_rows - 1, d.in.t0, d.in.rs, d.in.cs, a.perm};
   RowStore st{a.out + pol * a.out_pol_stride, r0, a.n_rows, N, a.sds, a.remap, a.scale,
               a.row_base, a.n_total, a.zs, a.nt};
   row_fft_tile<N, +1>(ld, st, a.tw, smem);

@@ -135,6 +135,20 @@ struct DadaIn {
 hipError_t launch_dada_unpack_rows(const DadaIn& d, int64_t n_rows, int C, int P, float2* out,
                                    int64_t out_pol_stride, hipStream_t s);
 
+// Channelised rows that lie strided in device memory (pfb_synthesis_execute_strided): element
+// (pol p, row t, channel c) at base[p * ps + t * rs + c * cs], n_dat rows; the launch's row 0
+// is row t0.  Only read; polarisations may interleave inside a row (ps < rs) or overlap.
+struct StridedIn {
+  const float2* base;
+  int64_t ps, rs, cs;
+  int64_t n_dat, t0;
+};
+// Rows [t0, t0 + n_rows) of such a layout -> out[pol][row][chan] packed (the strided-rows copy
+// kernel, pfb_layout.hip: the stitched head and the carry of a stream call, and the whole
+// input of a plan whose channel IFFT has no strided loader)
+hipError_t launch_strided_rows_copy(const StridedIn& d, int64_t n_rows, int C, int P, float2* out,
+                                    int64_t out_pol_stride, hipStream_t s);
+
 // Synthesis stage 1: per channelised time row, N-point inverse DFT across channels
 // (after the combine permutation and per-channel gain).  See DESIGN.md §synthesis.
 struct ChanIfftArgs {
@@ -151,9 +165,14 @@ struct ChanIfftArgs {
   int zblk = 1;            // Z rows in runs of zblk (1, 2, 4) per t0 (SynthBlockArgs::zblk)
   // the rows come from a DADA section instead of `in` (chan_ifft_dada_supported; no perm / gain)
   const DadaIn* dada = nullptr;
+  // the rows come through a strided layout instead of `in` (chan_ifft_strided_supported; perm
+  // allowed, no gain)
+  const StridedIn* strided = nullptr;
 };
 // the channel IFFT has a loader for DADA sections of this sample size (row_fft_dada_kernel)
 bool chan_ifft_dada_supported(int N, int nbit);
+// the channel IFFT has a strided row loader for this size (row_fft_strided_kernel)
+bool chan_ifft_strided_supported(int N);
 
 // Synthesis stage 2: per block and group of t0, Nf-point FFT over time, kept-bin
 // selection with deripple gain and four-step twiddle, W-point inverse FFT,

@@ -186,6 +186,40 @@ hipError_t pfb::launch_dada_unpack_rows(const pfb::DadaIn& d, int64_t n_rows, in
 
 namespace {
 
+// ---------------------------------------------------------------- strided rows -> packed
+// out[p][t][c] = in[p ps + (t0 + t) rs + c cs] (t < n_rows, c < C; blockIdx.y = p): the rows
+// of a strided channelised input (pfb::StridedIn) as the packed [pol][t][chan] buffer the
+// synthesis' cf32 path reads.  One element per thread, coalesced stores; coalesced loads when
+// cs = 1.  Exactly the mapped elements are loaded.
+__global__ void __launch_bounds__(TPB) strided_rows_copy_kernel(const float2* __restrict__ in, int64_t ps,
+                                                                int64_t rs, int64_t cs, int64_t t0,
+                                                                int64_t n_rows, int C,
+                                                                float2* __restrict__ out, int64_t ops) {
+  const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n_rows * C) return;
+  const int64_t p = blockIdx.y;
+  const int64_t t = i / C;
+  const int c = (int)(i - t * C);
+  out[p * ops + i] = in[p * ps + (t0 + t) * rs + c * cs];
+}
+
+}  // namespace
+
+hipError_t pfb::launch_strided_rows_copy(const pfb::StridedIn& d, int64_t n_rows, int C, int P, float2* out,
+                                         int64_t ops, hipStream_t s) {
+  if (n_rows <= 0) return hipSuccess;
+  if (!d.base || !out || d.ps <= 0 || d.rs <= 0 || d.cs <= 0 || d.t0 < 0 || d.t0 + n_rows > d.n_dat || C <= 0 ||
+      P <= 0 || P > 65535 || ops < n_rows * C)
+    return hipErrorInvalidValue;
+  const int64_t blocks = (n_rows * C + TPB - 1) / TPB;
+  if (blocks > INT32_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(strided_rows_copy_kernel, dim3((unsigned)blocks, (unsigned)P), dim3(TPB), 0, s, d.base, d.ps,
+                     d.rs, d.cs, d.t0, n_rows, C, out, ops);
+  return hipGetLastError();
+}
+
+namespace {
+
 // ---------------------------------------------------------------- gather / transpose
 // out[o][t][j] = in[o][t][src(j)], src(j) = src0 + j + (j >= split ? shift : 0)
 // (strides in complex samples): a contiguous channel range, or the two-stage

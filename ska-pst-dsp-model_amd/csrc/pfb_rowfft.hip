@@ -583,6 +583,56 @@ static hipError_t dispatch_row_fft_dada(int N, const RowFftArgs& r, const DadaIn
   }
 }
 
+// ----------------------------------------------------------------- strided row loader
+// (N = 4096 keeps its pair / persistent kernels and their buffer-descriptor loads: staged)
+bool chan_ifft_strided_supported(int N) { return chan_ifft_supported(N) && N != 4096; }
+
+template <int N, bool PERM>
+static hipError_t launch_row_fft_strided_t(const RowFftArgs& r, const StridedIn& in, int n_pol, hipStream_t s) {
+  constexpr int ROWS = RowShape<N>::ROWS;
+  const size_t bytes = ((size_t)ROWS * RowShape<N>::RS + tw_slots(N)) * sizeof(float2);
+  auto kern = row_fft_strided_kernel<N, PERM>;
+  hipError_t e = set_lds(kern, bytes);
+  if (e != hipSuccess) return e;
+  const int64_t tiles = (r.n_rows + ROWS - 1) / ROWS;
+  // row_fft_kernel's own grid (blockIdx.y = pol).  Polarisations closer than a 128-B line
+  // share lines inside every row (the inverse cascade's 112-B slices); handing 16 of them (16
+  // ps elements = a whole number of lines) to one XCD back to back (StridedRows) measured
+  // SLOWER at the SKA-Mid inverse cascade, 4096 x 14: 3.72-3.89 ms per call against 3.50-3.62
+  // in this order (profiles/twostage_inverse_order_ab.jsonl), so it is an experiments knob only
+  int share = 0;
+  if constexpr (kExperiments) {  // (PFB_STRIDED_SHARE=n: groups of n polarisations per XCD; A/B)
+    static const int forced = knob("PFB_STRIDED_SHARE") ? std::atoi(knob("PFB_STRIDED_SHARE")) : 0;
+    if (forced > 0) share = std::min(forced, n_pol);
+  }
+  if (share > 0) {
+    const int64_t gs = 8 * (int64_t)share;
+    const int64_t wgs = (tiles * n_pol + gs - 1) / gs * gs;
+    if (wgs > INT32_MAX) return hipErrorInvalidValue;
+    return launch_kernel(kern, dim3((unsigned)wgs), dim3(NT), bytes, s, r, StridedRows{in, tiles, n_pol, share});
+  }
+  if (tiles > INT32_MAX || n_pol > 65535) return hipErrorInvalidValue;
+  return launch_kernel(kern, dim3((unsigned)tiles, (unsigned)n_pol), dim3(NT), bytes, s, r,
+                       StridedRows{in, tiles, n_pol, 0});
+}
+
+static hipError_t dispatch_row_fft_strided(int N, const RowFftArgs& r, const StridedIn& in, int n_pol, hipStream_t s) {
+  switch (N) {
+#define PFB_STRIDED_N(n)                                                          \
+  case n:                                                                         \
+    return r.perm ? launch_row_fft_strided_t<n, true>(r, in, n_pol, s)            \
+                  : launch_row_fft_strided_t<n, false>(r, in, n_pol, s);
+    PFB_STRIDED_N(8) PFB_STRIDED_N(16) PFB_STRIDED_N(32) PFB_STRIDED_N(64) PFB_STRIDED_N(128)
+    PFB_STRIDED_N(256) PFB_STRIDED_N(512) PFB_STRIDED_N(1024) PFB_STRIDED_N(2048)
+    PFB_STRIDED_N(14) PFB_STRIDED_N(28) PFB_STRIDED_N(56) PFB_STRIDED_N(112) PFB_STRIDED_N(192)
+    PFB_STRIDED_N(216) PFB_STRIDED_N(224) PFB_STRIDED_N(384) PFB_STRIDED_N(432) PFB_STRIDED_N(448)
+    PFB_STRIDED_N(768) PFB_STRIDED_N(864) PFB_STRIDED_N(896) PFB_STRIDED_N(1536) PFB_STRIDED_N(1792)
+    PFB_STRIDED_N(3072) PFB_STRIDED_N(3584)
+#undef PFB_STRIDED_N
+    default: return hipErrorInvalidValue;
+  }
+}
+
 hipError_t launch_chan_ifft(const ChanIfftArgs& c, hipStream_t s) {
   if (c.n_rows <= 0) return hipSuccess;
   // (the stage-1 rows are read by the synthesis right after: default store policy while they
@@ -608,6 +658,14 @@ hipError_t launch_chan_ifft(const ChanIfftArgs& c, hipStream_t s) {
                       : dispatch_row_fft_dada<int8_t, false>(c.N, r, d, c.n_pol, s);
     return d.lowcbf ? dispatch_row_fft_dada<int16_t, true>(c.N, r, d, c.n_pol, s)
                     : dispatch_row_fft_dada<int16_t, false>(c.N, r, d, c.n_pol, s);
+  }
+  if (c.strided) {
+    const StridedIn& d = *c.strided;
+    // the loader has no gain instantiation, and reads rows [t0, t0 + n_rows) of the layout
+    if (c.cgain || !chan_ifft_strided_supported(c.N) || !d.base || d.ps <= 0 || d.rs <= 0 || d.cs <= 0 ||
+        d.t0 < 0 || d.t0 + c.n_rows > d.n_dat)
+      return hipErrorInvalidValue;
+    return dispatch_row_fft_strided(c.N, r, d, c.n_pol, s);
   }
   return dispatch_row_fft<+1>(c.N, r, c.n_pol, s);
 }

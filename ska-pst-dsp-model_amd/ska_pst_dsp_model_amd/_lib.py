@@ -44,6 +44,9 @@ PFB_DADA_LOWCBF = 1
 PFB_DADA_INPUT_NONE = 0
 PFB_DADA_INPUT_FUSED = 1
 PFB_DADA_INPUT_STAGED = 2
+PFB_STRIDED_INPUT_NONE = 0
+PFB_STRIDED_INPUT_IN_PLACE = 1
+PFB_STRIDED_INPUT_STAGED = 2
 
 _STATUS_NAMES = {
     0: "PFB_OK", 1: "PFB_ERR_INVALID_ARG", 2: "PFB_ERR_UNSUPPORTED", 3: "PFB_ERR_HIP",
@@ -124,6 +127,13 @@ SYMBOLS = [
                                                       c_int64, c_void_p, c_int64, c_int64,
                                                       POINTER(c_int64), c_void_p]),
     ("pfb_synthesis_last_dada_input", c_int32, [c_void_p]),
+    ("pfb_synthesis_execute_strided", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                                c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                                POINTER(c_int64), c_void_p]),
+    ("pfb_inverse_filterbank_execute_strided", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                                         c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                                         POINTER(c_int64), c_void_p]),
+    ("pfb_synthesis_last_strided_input", c_int32, [c_void_p]),
     ("pfb_dada_pack", c_int32, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int32,
                                 c_void_p]),
     ("pfb_gather_channels", c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,

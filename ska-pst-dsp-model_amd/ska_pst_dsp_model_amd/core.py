@@ -455,6 +455,54 @@ class SynthesisPlan:
                 byref(n_out), stream))
         return out[:, :n_out.value]
 
+    def execute_view(self, x, sample_offset: int = 1, stateful: bool = False, out=None):
+        """The synthesis of a strided view: ``x`` is any complex64 device tensor view shaped
+        (n_pol, n_dat, n_chan); its strides and storage offset go to the C ABI as they are
+        (``pfb_synthesis_execute_strided`` / ``pfb_inverse_filterbank_execute_strided``) and
+        no ``.contiguous()`` copy is made.  Bit for bit ``execute(x.contiguous(),
+        layout="ptc")``; ``last_strided_input()`` tells whether the channel IFFT read the
+        view in place."""
+        t = _torch()
+        if not is_device_array(x) or x.dtype != t.complex64 or x.dim() != 3:
+            raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG,
+                                "execute_view: expects a complex64 device tensor (n_pol, n_dat, n_chan)")
+        if x.shape[0] != self.n_pol or x.shape[2] != self.n_chan:
+            raise ValueError(f"plan built for (n_pol={self.n_pol}, n_chan={self.n_chan}), "
+                             f"got {tuple(x.shape)} [pol, time, chan]")
+        n_dat = int(x.shape[1])
+        if stateful:
+            cap = self.output_length(self.buffered_samples + n_dat)
+        else:
+            cap = self.output_length(max(n_dat - (int(sample_offset) - 1), 0))
+        if out is None:
+            out = t.empty((self.n_pol, max(cap, 0)), dtype=t.complex64, device=x.device)
+        elif (out.dtype != t.complex64 or out.device != x.device or not out.is_contiguous()
+              or out.dim() != 2 or out.shape[0] != self.n_pol):
+            raise ValueError(f"out must be a contiguous complex64 ({self.n_pol}, n) tensor on {x.device}, "
+                             f"got {tuple(out.shape)} {out.dtype} {out.device}")
+        width = out.shape[1]
+        # elements available from the view's first element to the end of its storage
+        in_cap = x.untyped_storage().nbytes() // x.element_size() - x.storage_offset()
+        ps, rs, cs = (int(v) for v in x.stride())
+        src, dst, stream = c_void_p(x.data_ptr()), c_void_p(out.data_ptr()), _stream_of(x, self)
+        n_out = c_int64(0)
+        if stateful:
+            _lib.check(self._lib.pfb_inverse_filterbank_execute_strided(
+                self._h, src, ps, rs, cs, in_cap, n_dat, dst, width, width, byref(n_out), stream))
+        else:
+            _lib.check(self._lib.pfb_synthesis_execute_strided(
+                self._h, src, ps, rs, cs, in_cap, n_dat, int(sample_offset), dst, width, width,
+                byref(n_out), stream))
+        return out[:, :n_out.value]
+
+    def last_strided_input(self) -> str:
+        """How the plan's last strided call read its rows: 'in_place' (the channel IFFT
+        loaded through the layout), 'staged' (copied to a packed buffer first), 'none' (no
+        strided call, or a packed or DADA call since) — pfb_synthesis_last_strided_input."""
+        m = int(self._lib.pfb_synthesis_last_strided_input(self._h))
+        return {_lib.PFB_STRIDED_INPUT_IN_PLACE: "in_place",
+                _lib.PFB_STRIDED_INPUT_STAGED: "staged"}.get(m, "none")
+
     def last_dada_input(self) -> str:
         """How the plan's last DADA call read its section: 'fused' (the channel IFFT read
         the file's own bytes), 'staged' (unpacked first), 'none' (no DADA call, or a cf32

@@ -200,6 +200,19 @@ class InverseFilterBank(DeChannelizer):
         out = plan.execute(input, stateful=True)
         return self, out[:, None, :]
 
+    def execute_view(self, view):
+        """``execute`` of the next chunk read where it lies: ``view`` is a complex64 device
+        tensor view in engine order (n_pol, n_dat, n_chan) with any positive strides (the
+        coarse-channel slices of a two-stage product, a channel window, channel-major
+        rows).  Same output and carry as ``execute(view.transpose(1, 2))``, bit for bit,
+        with no packed copy of the view (``SynthesisPlan.execute_view``)."""
+        if int(self.sample_offset) < 0:
+            raise ValueError("sample_offset is 0-based (>= 0)")
+        plan = self._ensure_plan(int(view.shape[0]), int(view.shape[2]))
+        plan.set_stream_sample_offset(int(self.sample_offset))
+        out = plan.execute_view(view, stateful=True)
+        return self, out[:, None, :]
+
     def execute_dada(self, raw, nbit: int, ndim: int = 2, lowcbf: bool = False, n_pol: int = 1):
         """``execute`` of the next chunk as the file holds it: ``raw`` is a device tensor of
         the DADA section's bytes (``DADARead.generate_raw``), ``nchan`` channels x ``n_pol``
@@ -373,11 +386,30 @@ class TwoStageInverseFilterBank(DeChannelizer):
     """TwoStageInverseFilterBank.m:1-159 — stage-2 inversion per output coarse channel.
 
     The nch_out InverseFilterBank objects of the Matlab loop (:124-151) become ONE
-    batched synthesis plan over nch_out "polarisations": one gather
-    (``pfb_gather_channels``) slices the nch_in = nch2 * combine fine channels of every
-    coarse channel, one synthesis call inverts them all."""
+    batched synthesis plan over nch_out "polarisations" and one synthesis call inverts
+    them all.  The nch_in = nch2 * combine fine channels of coarse channel o are channels
+    [o nch_in, (o + 1) nch_in) of every input row.  ``strided_input``: the plan reads them
+    where they lie, as the (nch_out, T, nch_in) view with strides (nch_in, nchan, 1)
+    (``pfb_inverse_filterbank_execute_strided``; a spectral taper goes through that call's
+    staged path); otherwise one gather (``pfb_gather_channels``) copies the slices into
+    [coarse][t][nch_in] first.  Both compute the same values, bit for bit."""
+
+    # strided input by default, per shape class: "narrow" = slices shorter than a 128-B line
+    # (nch_in < 16: neighbouring coarse channels share lines), "wide" = the rest.  True only
+    # where it measured faster than the gather by more than the gather's own spread: both
+    # did, the SKA-Mid inverse 4096 x 14 and the 256 x 256 cascade (DESIGN.md §6,
+    # profiles/twostage_inverse_strided_ab.jsonl)
+    _STRIDED_INPUT_DEFAULT = {"narrow": True, "wide": True}
+
+    def _use_strided_input(self, nch_in: int) -> bool:
+        if self.strided_input is not None:
+            return bool(self.strided_input)
+        return self._STRIDED_INPUT_DEFAULT["narrow" if nch_in < 16 else "wide"]
 
     def __init__(self, config, device: int = 0):
+        # True / False: read the coarse-channel slices in place / gather them first (A/B
+        # runs); None: the measured default of the shape class (_STRIDED_INPUT_DEFAULT)
+        self.strided_input = None
         self.config1 = config
         self.config2 = config
         self.stage1 = InverseFilterBank(config, device=device)
@@ -410,6 +442,7 @@ class TwoStageInverseFilterBank(DeChannelizer):
         return self
 
     def execute(self, input):  # noqa: A002
+        import torch
         if not self.built:
             self.build()
         x, host = _to_device(input, self.device)
@@ -436,11 +469,20 @@ class TwoStageInverseFilterBank(DeChannelizer):
         buf = x.transpose(1, 2)                   # (npol, T, nchan) engine order
         if buf.stride(2) != 1:
             buf = buf.contiguous()
-        sliced = layout.gather_channels(buf[0], n_outer=nch_out, in_outer_stride=nch_in,
-                                        in_row_stride=buf.stride(1), n_rows=T, n_sel=nch_in)
+        if buf.dtype != torch.complex64:
+            buf = buf.to(torch.complex64)
         st = self.stage2
         st.critical = critical
         st.combine = self.combine
-        _, tmp = st.execute(sliced.transpose(1, 2))  # (nch_out, 1, T_out)
+        if self._use_strided_input(nch_in):
+            # coarse channel o = channels [o nch_in, (o + 1) nch_in) of every row, read where
+            # they lie: (nch_out, T, nch_in) with strides (nch_in, row stride, 1)
+            rows = buf[0][:, :nch_out * nch_in]
+            view = rows.unflatten(1, (nch_out, nch_in)).permute(1, 0, 2)
+            _, tmp = st.execute_view(view)            # (nch_out, 1, T_out)
+        else:
+            sliced = layout.gather_channels(buf[0], n_outer=nch_out, in_outer_stride=nch_in,
+                                            in_row_stride=buf.stride(1), n_rows=T, n_sel=nch_in)
+            _, tmp = st.execute(sliced.transpose(1, 2))  # (nch_out, 1, T_out)
         out = tmp.reshape(1, nch_out, tmp.shape[2])
         return self, (_to_host(out) if host else out)
