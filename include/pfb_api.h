@@ -369,6 +369,45 @@ pfb_status pfb_inverse_filterbank_execute_dada(pfb_synthesis_plan* plan, const v
                                                int64_t out_capacity, int64_t* n_out, void* stream);
 int32_t pfb_synthesis_last_dada_input(const pfb_synthesis_plan* plan);
 
+/* Analysis straight from a single-channel DADA data section (DADARead.m:58-83 followed by
+ * polyphase_analysis / FilterBank.m:65-128): what a file or a beamformer delivers for one
+ * channel, [t][pol][re, im] with the polarisations alternating sample by sample.  Device
+ * memory only.  `in` holds n_dat (n_in) samples x 1 channel x the plan's n_pol x ndim values
+ * of nbit, in `order` (pfb_dada_order); in TFP order complex sample t of polarisation p is
+ * element t * n_pol + p.  The output, *n_out, the status codes, pfb_filterbank_buffered,
+ * pfb_filterbank_output_rows and the stream state are those of pfb_dada_unpack into a packed
+ * [pol][t] buffer followed by pfb_analysis_execute / pfb_filterbank_execute, bit for bit: the
+ * integer-to-float cast is exact and the FIR sums run in the same order.  Every check (NBIT
+ * 8/16/32/64, NDIM 1/2, the order, LowCBF rows a multiple of 32, null buffers, and the
+ * capacity and stride checks of the cf32 calls) runs before any launch or state change: a
+ * rejected stream call leaves the carry untouched, and a rejected call on a
+ * PFB_ANALYSIS_LOWCBF plan leaves the first-call pre-padding pending (pfb_analysis_variant).
+ * cf32 and DADA stream calls may alternate on one plan: the carry stays packed cf32.
+ * FUSED: the analysis kernel loads the section's bytes itself, one range-checked buffer load
+ * of 2 / 4 / 8 bytes per complex sample, and no unpacked copy crosses HBM — NBIT 8, 16
+ * (integers) and 32 (float), NDIM 2, TFP order, a section aligned to one complex sample, and a
+ * plan on the streaming kernel (PFB_ANALYSIS_BUNTON with n_chan 256, os 8/7 or 4/3, 12 or 13
+ * tap phases, and PFB_ANALYSIS_LOWCBF; stateless and stream calls — a stream call reads the
+ * carry through its cf32 descriptor in the same launch) or on the LDS-shared FIR of the
+ * n_chan > 256 path (os 8/7 or 4/3, <= 32 phases; the stateless call, and a stream call with
+ * nothing buffered).  No byte outside the section is loaded, and of a two-polarisation section
+ * a workgroup loads only its own polarisation's samples.  STAGED: every other format (NBIT
+ * 64, NDIM 1, LowCBF order, a misaligned section), plan or stream state is unpacked into a
+ * plan-owned buffer — a stream call's samples straight behind the carry in the concatenation
+ * buffer — and runs the cf32 path, so these calls accept every plan the cf32 calls accept.
+ * pfb_analysis_last_dada_input: which of the two the plan's last DADA call took, NONE before
+ * one or after a cf32 call, -1 for a null plan.  (Measured A/B against the unpack-then-execute
+ * pair: DESIGN.md §4.6.) */
+pfb_status pfb_analysis_execute_dada(pfb_analysis_plan* plan, const void* in, int32_t nbit,
+                                     int32_t ndim, int32_t order, int64_t n_dat, pfb_cf32* out,
+                                     int64_t out_pol_stride, int64_t out_capacity, int64_t* n_out,
+                                     void* stream);
+pfb_status pfb_filterbank_execute_dada(pfb_analysis_plan* plan, const void* in, int32_t nbit,
+                                       int32_t ndim, int32_t order, int64_t n_in, pfb_cf32* out,
+                                       int64_t out_pol_stride, int64_t out_capacity, int64_t* n_out,
+                                       void* stream);
+int32_t pfb_analysis_last_dada_input(const pfb_analysis_plan* plan);
+
 /* The synthesis calls reading their channelised rows strided (device memory only): channel c
  * of row t of polarisation p is in[p * in_pol_stride + t * in_row_stride + c * in_chan_stride]
  * — the input-side mirror of pfb_filterbank_execute_strided.  Polarisations may interleave

@@ -8,6 +8,9 @@ one MI355X, as algorithmic HBM bytes / time against the 8 TB/s peak.
   * two-stage analysis cascade (256 x 256 ch; stage 2 batched over 256 series)
   * --only-dada: synthesis from a DADA section at the C2 shape, the staged pair
     (pfb_dada_unpack + pfb_synthesis_execute) against pfb_synthesis_execute_dada, interleaved
+  * --only-dada-analysis: analysis from a single-channel DADA section (C2, LowCBF, SKA-Mid
+    stage 1), the staged pair (pfb_dada_unpack + pfb_analysis_execute) against
+    pfb_analysis_execute_dada, interleaved
   * --only-twostage-inverse: TwoStageInverseFilterBank with the channel gather against the
     strided input (pfb_inverse_filterbank_execute_strided), interleaved
 
@@ -53,10 +56,13 @@ def main():
     ap.add_argument("--only-twostage", action="store_true")
     ap.add_argument("--only-dada", action="store_true",
                     help="the dada_synthesis A/B alone (--reps: calls per timed window)")
+    ap.add_argument("--only-dada-analysis", action="store_true",
+                    help="the dada_analysis A/B alone (--reps: calls per timed window)")
     ap.add_argument("--only-twostage-inverse", action="store_true",
                     help="the inverse cascade's gather vs strided-input A/B alone (--reps: calls per window)")
     ap.add_argument("--rounds", type=int, default=15,
-                    help="--only-dada / --only-twostage-inverse: interleaved A/B windows per case")
+                    help="--only-dada / --only-dada-analysis / --only-twostage-inverse: interleaved A/B "
+                         "windows per case")
     ap.add_argument("--padded-cascade", default="default",
                     choices=["default", "strided", "no-stage1", "no-stage2", "gather"],
                     help="the SKA-Mid padded cascade's stores: the library default; both stages strided; "
@@ -88,6 +94,8 @@ def main():
         return twostage(torch, pfb, noise, args.reps, args.padded_cascade)
     if args.only_dada:
         return dada_synthesis(torch, pfb, dev, max(args.reps, 20), args.rounds)
+    if args.only_dada_analysis:
+        return dada_analysis(torch, pfb, dev, max(args.reps, 20), args.rounds)
     if args.only_twostage_inverse:
         return twostage_inverse(torch, pfb, noise, max(args.reps, 20), max(args.rounds, 5))
     # ---- C2' (4/3) round trip
@@ -251,6 +259,86 @@ def dada_synthesis(torch, pfb, dev, reps, rounds):
                 "B_first_pass_bytes_per_sample": 2 * nbit // 8,
                 "samples": samples}), flush=True)
         del syn, out_a, out_b, x
+
+
+def dada_analysis(torch, pfb, dev, reps, rounds):
+    """Single-channel DADA section (TFP, pols interleaved) -> channelised product.  A:
+    pfb_dada_unpack into a packed cf32 [pol][t] buffer, then pfb_analysis_execute (the calls a
+    caller had before).  B: pfb_analysis_execute_dada.  Both through the C ABI into
+    preallocated buffers.  The outputs are asserted equal first; then `rounds` windows of `reps`
+    calls of each side, alternating A and B in one process, after a warm-up of both.  One line
+    per case with the median, min, max and quartiles of each side's per-call time."""
+    from ctypes import byref, c_int64, c_void_p
+    from ska_pst_dsp_model_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator(device=dev).manual_seed(3)
+    taps87 = pfb.design_PFB_FIR_filter(256, "8/7", 12)
+    taps_pst = pfb.read_fir_filter_coeff(os.path.join(pfb.config.config_dir, "PST_filtertaps.txt"))
+    # (the SKA-Mid stage 1's tap count; the values do not bear on the time)
+    taps_mid = np.random.default_rng(4).standard_normal(4096 * 24 + 2049) / 4096
+    cases = [("C2 256ch 8/7", taps87, 256, "8/7", "polyphase_analysis", 1 << 24, nbit, n_pol)
+             for nbit in (8, 16, 32) for n_pol in (1, 2)]
+    cases.append(("LowCBF PST filterbank", taps_pst, 256, "4/3", "polyphase_analysis_lowcbf", 1 << 24, 8, 2))
+    cases.append(("SKA-Mid stage 1 4096ch 8/7 padded", taps_mid, 4096, "8/7", "polyphase_analysis_padded",
+                  1 << 26, 16, 1))
+    dts = {8: torch.int8, 16: torch.int16}
+    for shape, taps, N, os_, variant, n, nbit, n_pol in cases:
+        plan = pfb.AnalysisPlan(taps, N, os_, variant, n_pol)
+        if variant.endswith("lowcbf"):
+            plan.execute(torch.zeros((n_pol, 4096), dtype=torch.complex64, device=dev))  # the one-time padding
+        K, C = plan.output_length(n), plan.out_chan
+        if nbit == 32:
+            raw = torch.randn((n * n_pol * 2,), device=dev, generator=g)
+        else:
+            lim = 1 << (nbit - 1)
+            raw = torch.randint(-lim, lim, (n * n_pol * 2,), dtype=dts[nbit], device=dev, generator=g)
+        x = torch.empty((n_pol, n), dtype=torch.complex64, device=dev)
+        out_a = torch.empty((n_pol, K, C), dtype=torch.complex64, device=dev)
+        out_b = torch.empty_like(out_a)
+        stream = c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        n_out = c_int64(0)
+
+        def side_a():
+            _lib.check(lib.pfb_dada_unpack(c_void_p(raw.data_ptr()), nbit, 2, _lib.PFB_DADA_TFP, n, 1, n_pol,
+                                           c_void_p(x.data_ptr()), n, stream))
+            _lib.check(lib.pfb_analysis_execute(plan._h, c_void_p(x.data_ptr()), n, n, c_void_p(out_a.data_ptr()),
+                                                K * C, K, byref(n_out), _lib.PFB_MEM_DEVICE, stream))
+
+        def side_b():
+            _lib.check(lib.pfb_analysis_execute_dada(plan._h, c_void_p(raw.data_ptr()), nbit, 2, _lib.PFB_DADA_TFP,
+                                                     n, c_void_p(out_b.data_ptr()), K * C, K, byref(n_out),
+                                                     stream))
+
+        side_a()
+        side_b()
+        path = plan.last_dada_input()
+        torch.cuda.synchronize()
+        assert n_out.value == K and torch.equal(out_a, out_b), f"dada_analysis {shape} {nbit}: outputs differ"
+        for _ in range(2):
+            timeit(torch, side_a, reps)
+            timeit(torch, side_b, reps)
+        ta, tb = [], []
+        for _ in range(rounds):
+            ta.append(timeit(torch, side_a, reps))
+            tb.append(timeit(torch, side_b, reps))
+
+        def stats(t):
+            q = np.percentile(t, [0, 25, 50, 75, 100])
+            return {k: round(float(v), 4) for k, v in zip(("min", "q25", "median", "q75", "max"), q)}
+        a, b = stats(ta), stats(tb)
+        esz = 2 * nbit // 8
+        print(json.dumps({
+            "kernel": "dada_analysis", "shape": shape, "samples": n, "n_pol": n_pol, "nbit": nbit, "path": path,
+            "calls_per_window": reps, "windows": rounds, "outputs_equal": True,
+            "A_unpack_then_execute_ms": a, "B_execute_dada_ms": b,
+            "A_spread_ms": round(a["max"] - a["min"], 4),
+            "B_below_A_by_ms": round(a["median"] - b["median"], 4),
+            "B_over_A": round(b["median"] / a["median"], 4),
+            "stays_fused": bool(a["median"] - b["median"] > a["max"] - a["min"]),
+            "A_bytes": int(n_pol * (n * (esz + 8 + 8) + K * C * 8)),
+            "B_bytes": int(n_pol * (n * esz + K * C * 8))}), flush=True)
+        del plan, raw, x, out_a, out_b
+        torch.cuda.empty_cache()
 
 
 def twostage_inverse(torch, pfb, noise, reps, rounds):

@@ -39,6 +39,55 @@ struct StreamShape {
   static constexpr size_t lds_bytes = (size_t)F_OFF * sizeof(float) + F_LEN * sizeof(float);
 };
 
+// The input fetch of the analysis kernels that read a series through a buffer descriptor
+// (analysis_stream_body, fir_lds_body): kBytes per complex sample, one range-checked buffer
+// load each (raw_t: what the prefetch registers hold), converted to (re, im) float when the
+// sample enters the FIR.  InCf32: the packed [pol][t] complex float32 series.  InDada8 / 16 /
+// 32: a single-channel DADA section in TFP order, NDIM 2 (AnalysisArgs::din), read in place —
+// sample t of polarisation p at byte ((t n_pol + p) kBytes); the integer cast is exact and a
+// load outside the descriptor returns 0 = 0.0f, so the FIR sees the values pfb_dada_unpack
+// would have written.
+struct InCf32 {
+  static constexpr bool kDada = false;
+  static constexpr int kBytes = 8;
+  using raw_t = v2f;
+  template <int AUX>
+  static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t off) {
+    return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, AUX));
+  }
+  static __device__ __forceinline__ raw_t gload(const void* p) { return *reinterpret_cast<const v2f*>(p); }
+  static __device__ __forceinline__ v2f cvt(raw_t v) { return v; }
+};
+struct InDada32 : InCf32 {  // NBIT 32: float (re, im), pols interleaved
+  static constexpr bool kDada = true;
+};
+struct InDada16 {  // NBIT 16: int16 (re, im)
+  static constexpr bool kDada = true;
+  static constexpr int kBytes = 4;
+  using raw_t = uint32_t;
+  template <int AUX>
+  static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t off) {
+    return __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, AUX);
+  }
+  static __device__ __forceinline__ raw_t gload(const void* p) { return *reinterpret_cast<const uint32_t*>(p); }
+  static __device__ __forceinline__ v2f cvt(raw_t v) {
+    return v2f{(float)(int16_t)(v & 0xffffu), (float)(int16_t)(v >> 16)};
+  }
+};
+struct InDada8 {  // NBIT 8: int8 (re, im)
+  static constexpr bool kDada = true;
+  static constexpr int kBytes = 2;
+  using raw_t = uint16_t;
+  template <int AUX>
+  static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t off) {
+    return __builtin_amdgcn_raw_buffer_load_b16(r, off, 0, AUX);
+  }
+  static __device__ __forceinline__ raw_t gload(const void* p) { return *reinterpret_cast<const uint16_t*>(p); }
+  static __device__ __forceinline__ v2f cvt(raw_t v) {
+    return v2f{(float)(int8_t)(v & 0xffu), (float)(int8_t)(v >> 8)};
+  }
+};
+
 // ZOUT (round trip): each step's channelised rows are also inverse-transformed across
 // channels in LDS and written as synthesis stage-1 rows (AnalysisArgs::z), so the
 // synthesis does not re-read them from HBM.
@@ -79,7 +128,8 @@ struct SinkStore {
 // wave w owns rows 4w .. 4w + 3 for the whole transform (wave_rows_ok) and the two barriers
 // inside it are wave barriers (round 6; timing variants r06_v14: the FFT was 30 of the
 // kernel's 78 us with four workgroup barriers a step, memory traffic masked or not)
-template <int N, int P, int NU, int DE, int ZOUT, bool LCBF, int GS, int TV = 0>
+// IN: the input fetch (InCf32, or a DADA section read in place)
+template <int N, int P, int NU, int DE, int ZOUT, bool LCBF, int GS, int TV = 0, class IN = InCf32>
 __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int pol, int w, int nw) {
   using SH = StreamShape<N, P, NU, DE>;
   constexpr int M = SH::M, PE = SH::PE, QS = SH::QS, T = SH::T, NEW = SH::NEW, WIN = SH::WIN;
@@ -92,11 +142,24 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
     // thousand samples are a fraction of one row of work per workgroup); before any early
     // return, so every workgroup takes its share
     // (a uniform loop with a per-lane guard — no lane-dependent trip count)
-    const float2* src = a.in + pol * a.in_pol_stride + a.carry_src;
     float2* dst = a.carry_out + pol * a.carry_pol_stride;
+    if constexpr (IN::kDada) {
+      // (the carry stays packed cf32: converted as it is copied)
+      const int64_t step = (int64_t)a.n_pol * IN::kBytes;
+      const char* src = static_cast<const char*>(a.din) + pol * IN::kBytes + a.carry_src * step;
+      for (int64_t i0 = (int64_t)w * NT; i0 < a.carry_n; i0 += (int64_t)nw * NT) {
+        const int64_t i = i0 + c;
+        if (i < a.carry_n) {
+          const v2f v = IN::cvt(IN::gload(src + i * step));
+          dst[i] = make_float2(v.x, v.y);
+        }
+      }
+    } else {
+    const float2* src = a.in + pol * a.in_pol_stride + a.carry_src;
     for (int64_t i0 = (int64_t)w * NT; i0 < a.carry_n; i0 += (int64_t)nw * NT) {
       const int64_t i = i0 + c;
       if (i < a.carry_n) dst[i] = src[i];
+    }
     }
   }
   }
@@ -108,7 +171,6 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
 
   // input column c from row DE q_first on; range-checked buffer loads return 0 past n_dat
   const int64_t row_first = (int64_t)DE * (q_lo + st0 * QS);
-  const float2* xpol = a.in + pol * a.in_pol_stride;
   // window row r, column c is x[(row_first + r) N + c - pad]: the descriptor starts at the
   // first real sample the range reads; pre-padding rows give negative offsets, which wrap
   // past the range check and read as zeros
@@ -118,15 +180,29 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
   const int64_t avail = a.n_dat - gb;
   // the launcher sizes the ranges so that a workgroup's rows span <= kRsrcMaxBytes
   // (launch_stream); the min() only bounds the series tail beyond the range
-  uint32_t nbytes = (uint32_t)min(max(avail, (int64_t)0) * 8, kRsrcMaxBytes);
+  uint32_t nbytes;
+  const void* xb;
+  // bytes from one sample of this polarisation to its next
+  int sstep = 8;
+  if constexpr (IN::kDada) {
+    // a DADA section: the descriptor starts at this polarisation's sample gb and ends with
+    // the last byte of its last sample, and every offset is a multiple of the step — no
+    // byte of the partner polarisation, and none outside the section, is loaded
+    sstep = a.n_pol * IN::kBytes;
+    xb = static_cast<const char*>(a.din) + pol * IN::kBytes + gb * (int64_t)sstep;
+    nbytes = avail > 0 ? (uint32_t)min((avail - 1) * (int64_t)sstep + IN::kBytes, kRsrcMaxBytes) : 0u;
+  } else {
+    xb = a.in + pol * a.in_pol_stride + gb;
+    nbytes = (uint32_t)min(max(avail, (int64_t)0) * 8, kRsrcMaxBytes);
+  }
   if (tmask(a.timing_mask) & 1) nbytes = 0;
-  const __amdgpu_buffer_rsrc_t xr = make_rsrc(xpol + gb, nbytes);
+  const __amdgpu_buffer_rsrc_t xr = make_rsrc(xb, nbytes);
   // rows past the last window of the range (the unconditional last prefetch) re-read the
   // last row instead: an L2 hit rather than HBM traffic nobody uses
   const int r_last = (int)(st1 - st0 - 1) * NEW + WIN - 1;
   auto ld = [&](int r) {  // window row r (relative to row_first)
-    const v2u v = __builtin_amdgcn_raw_buffer_load_b64(xr, (uint32_t)((min(r, r_last) * N + c + shift) * 8), 0, kAuxIn);
-    return __builtin_bit_cast(v2f, v);
+    if constexpr (IN::kDada) return IN::template load<kAuxIn>(xr, (uint32_t)((min(r, r_last) * N + c + shift) * sstep));
+    else return IN::template load<kAuxIn>(xr, (uint32_t)((min(r, r_last) * N + c + shift) * 8));
   };
   // (re, im) as a packed pair: one v_pk_fma_f32 per complex x real tap MAC
   v2f win[WIN];
@@ -139,11 +215,11 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
 #pragma unroll
     for (int i = 0; i < WIN; ++i) {
       const v2u pv = __builtin_amdgcn_raw_buffer_load_b64(pr, (uint32_t)(((row_first + i) * N + c) * 8), 0, 0);
-      win[i] = ld(i) + __builtin_bit_cast(v2f, pv);
+      win[i] = IN::cvt(ld(i)) + __builtin_bit_cast(v2f, pv);
     }
   } else {
 #pragma unroll
-    for (int i = 0; i < WIN; ++i) win[i] = ld(i);
+    for (int i = 0; i < WIN; ++i) win[i] = IN::cvt(ld(i));
   }
 
   // LDS: twiddles behind the FFT rows, then F = [N zeros, taps, zeros]
@@ -164,7 +240,8 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
     // (unconditional: past the range it reads rows nobody uses, or zeros past n_dat —
     // a conditional prefetch makes vmcnt path-dependent and the next step waits for
     // every store as well)
-    v2f pf[NEW];
+    // (a DADA section: the packed file values, converted when the window slides)
+    typename IN::raw_t pf[NEW];
 #pragma unroll
     for (int i = 0; i < NEW; ++i) pf[i] = ld(rel + WIN + i);
     __syncthreads();  // previous step's FFT has read its rows (first step: F staged)
@@ -281,7 +358,7 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
 #pragma unroll
     for (int i = 0; i < PE - 1; ++i) win[i] = win[i + NEW];
 #pragma unroll
-    for (int i = 0; i < NEW; ++i) win[PE - 1 + i] = pf[i];
+    for (int i = 0; i < NEW; ++i) win[PE - 1 + i] = IN::cvt(pf[i]);
     }
   }
 }
@@ -292,6 +369,16 @@ template <int N, int P, int NU, int DE, int ZOUT, bool LCBF = false, int GS = 0,
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE))) void analysis_stream_kernel(AnalysisArgs a) {
   const int w = a.linear ? (int)blockIdx.x : xcd_tile(blockIdx.x, gridDim.x);
   analysis_stream_body<N, P, NU, DE, ZOUT, LCBF, GS, TV>(a, blockIdx.y, w, gridDim.x);
+}
+
+// The same kernel reading a DADA section in place (IN: InDada8 / 16 / 32; AnalysisArgs::din):
+// the plain channelised product ([k][c], or the LowCBF 216 channels), stateless or stream
+// calls — the carry comes through the cf32 `pre` descriptor as ever.  A kernel of its own
+// name, so the cf32 kernels' symbols — the keys of the recorded profiles — stay as they are.
+template <int N, int P, int NU, int DE, bool LCBF, class IN>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void analysis_stream_dada_kernel(AnalysisArgs a) {
+  const int w = a.linear ? (int)blockIdx.x : xcd_tile(blockIdx.x, gridDim.x);
+  analysis_stream_body<N, P, NU, DE, 0, LCBF, 0, 0, IN>(a, blockIdx.y, w, gridDim.x);
 }
 
 }  // namespace pfb

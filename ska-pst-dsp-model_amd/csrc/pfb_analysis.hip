@@ -397,8 +397,10 @@ struct FirLdsShape {
 
 // PFD: iterations of input rows held in registers ahead of the ring (1; 2 — twice the bytes
 // in flight per workgroup — was measured no faster in rounds 1 and 4 and its knob retired)
-template <int PW, int DE, int NU, int VARIANT, int PFD = 1>
-__global__ __launch_bounds__(NT) void fir_lds_kernel(AnalysisArgs a, int ranges, int cs, int xcd) {
+// IN: the input fetch (pfb_ana_stream.hpp: InCf32, or a DADA section read in place — the
+// prefetch registers then hold the packed file values, converted on their way into the ring)
+template <int PW, int DE, int NU, int VARIANT, int PFD = 1, class IN = InCf32>
+__device__ __forceinline__ void fir_lds_body(const AnalysisArgs& a, int ranges, int cs, int xcd) {
   using SH = FirLdsShape<NU, DE>;
   constexpr int CW = SH::CW, U = SH::U, RR = SH::RR, CWP = SH::CWP, NPF = SH::NPF, MIR = SH::MIR;
   constexpr int NJ = (PW + DE - 1) / DE;  // outputs a sample contributes to
@@ -453,16 +455,27 @@ __global__ __launch_bounds__(NT) void fir_lds_kernel(AnalysisArgs a, int ranges,
 
   // input descriptor from the lowest row the range touches (samples outside [0, n_dat)
   // read as 0 through the range check; the launcher keeps the extent within a descriptor)
-  const float2* xpol = a.in + pol * a.in_pol_stride;
   const int64_t rho_min = (int64_t)DE * qw + e_min - DE;
   const int64_t b0 = max((int64_t)0, rho_min * N);
   const int64_t avail = a.n_dat - b0;
-  const __amdgpu_buffer_rsrc_t xr =
-      make_rsrc(xpol + b0, (uint32_t)min(max(avail, (int64_t)0) * 8, kRsrcMaxBytes));
+  // (a DADA section: from this polarisation's sample b0 to the last byte of its last sample,
+  // every offset a multiple of the step to its next sample — analysis_stream_body's note)
+  int64_t sstep = 8;
+  const void* xb;
+  uint32_t nbytes;
+  if constexpr (IN::kDada) {
+    sstep = (int64_t)a.n_pol * IN::kBytes;
+    xb = static_cast<const char*>(a.din) + pol * IN::kBytes + b0 * sstep;
+    nbytes = avail > 0 ? (uint32_t)min((avail - 1) * sstep + IN::kBytes, kRsrcMaxBytes) : 0u;
+  } else {
+    xb = a.in + pol * a.in_pol_stride + b0;
+    nbytes = (uint32_t)min(max(avail, (int64_t)0) * 8, kRsrcMaxBytes);
+  }
+  const __amdgpu_buffer_rsrc_t xr = make_rsrc(xb, nbytes);
   auto ld = [&](int64_t rho, int col) {  // x[rho N + col]
     const int64_t g = rho * N + col;
-    const v2u v = __builtin_amdgcn_raw_buffer_load_b64(xr, (uint32_t)((g - b0) * 8), 0, kNtlFir ? 2 : 0);
-    return __builtin_bit_cast(v2f, v);
+    if constexpr (IN::kDada) return IN::template load<(kNtlFir ? 2 : 0)>(xr, (uint32_t)((g - b0) * sstep));
+    else return IN::template load<(kNtlFir ? 2 : 0)>(xr, (uint32_t)((g - b0) * 8));
   };
   // taps by (new-sample slot i, lag j): padded i + j DE, Bunton PW - DE + i - j DE
   float f[PW];
@@ -471,10 +484,10 @@ __global__ __launch_bounds__(NT) void fir_lds_kernel(AnalysisArgs a, int ranges,
   // ring: rows (DE qw + e_min - DE, DE qw + e_max - DE] now; each iteration adds U DE rows
   for (int i = tid; i < (e_max - e_min) * CW; i += NT) {
     const int64_t rho = (int64_t)DE * (qw - 1) + e_min + 1 + i / CW;
-    ring_put(rho, i % CW, ld(rho, (c0 + i % CW + cs) % N));
+    ring_put(rho, i % CW, IN::cvt(ld(rho, (c0 + i % CW + cs) % N)));
   }
-  v2f pf[PFD][NPF];
-  auto prefetch = [&](int64_t qi, v2f* d) {  // rows (DE (qi - 1) + e_max, DE (qi - 1) + e_max + U DE]
+  typename IN::raw_t pf[PFD][NPF];
+  auto prefetch = [&](int64_t qi, typename IN::raw_t* d) {  // rows (DE (qi - 1) + e_max, DE (qi - 1) + e_max + U DE]
 #pragma unroll
     for (int j = 0; j < NPF; ++j) {
       const int i = min(tid + j * NT, SH::BATCH - 1);
@@ -518,7 +531,7 @@ __global__ __launch_bounds__(NT) void fir_lds_kernel(AnalysisArgs a, int ranges,
       const int i = tid + j * NT;
       if (i < SH::BATCH) {
         const int64_t rho = (int64_t)DE * (qi - 1) + e_max + 1 + i / CW;
-        ring_put(rho, i % CW, pf[0][j]);
+        ring_put(rho, i % CW, IN::cvt(pf[0][j]));
       }
     }
 #pragma unroll
@@ -553,6 +566,18 @@ __global__ __launch_bounds__(NT) void fir_lds_kernel(AnalysisArgs a, int ranges,
   }
 }
 
+template <int PW, int DE, int NU, int VARIANT, int PFD = 1>
+__global__ __launch_bounds__(NT) void fir_lds_kernel(AnalysisArgs a, int ranges, int cs, int xcd) {
+  fir_lds_body<PW, DE, NU, VARIANT, PFD>(a, ranges, cs, xcd);
+}
+
+// the same FIR reading a DADA section in place (AnalysisArgs::din): a kernel of its own name,
+// as analysis_stream_dada_kernel
+template <int PW, int DE, int NU, int VARIANT, class IN>
+__global__ __launch_bounds__(NT) void fir_lds_dada_kernel(AnalysisArgs a, int ranges, int cs, int xcd) {
+  fir_lds_body<PW, DE, NU, VARIANT, 1, IN>(a, ranges, cs, xcd);
+}
+
 template <int PW, int DE>
 static hipError_t launch_fir_lds_t(const AnalysisArgs& a, hipStream_t s) {
   constexpr int NU = DE == 7 ? 8 : 4;
@@ -566,7 +591,9 @@ static hipError_t launch_fir_lds_t(const AnalysisArgs& a, hipStream_t s) {
   int64_t ranges = std::max<int64_t>(1, std::min<int64_t>(target / chunks, nq / (4 * SH::U)));
   // one range reads rows [DE (q0 - NJ) + e_min - DE, DE q1 + e_max + 2 U DE]: within a descriptor
   const int64_t halo_rows = PW + 3 * DE + 3 * SH::U * DE + 2 * NU + 4;  // (3 U DE: PFD <= 2)
-  const int64_t fit_rows = kRsrcMaxBytes / 8 / a.N - halo_rows;
+  // (bytes from one sample of a series to its next: 8, or a DADA section's n_pol x 2 x NBIT / 8)
+  const int64_t sstep = a.din ? (int64_t)a.n_pol * (a.din_nbit / 4) : 8;
+  const int64_t fit_rows = kRsrcMaxBytes / sstep / a.N - halo_rows;
   if (fit_rows <= 0) return hipErrorInvalidValue;
   ranges = std::max(ranges, (nq * DE + fit_rows - 1) / fit_rows);
   if (ranges * chunks > INT32_MAX) return hipErrorInvalidValue;
@@ -576,6 +603,18 @@ static hipError_t launch_fir_lds_t(const AnalysisArgs& a, hipStream_t s) {
   static const bool no_zalign = knob("PFB_FIR_ZALIGN") && std::atoi(knob("PFB_FIR_ZALIGN")) == 0;
   const int cs = (a.variant == kPadded && a.z && !no_zalign) ? a.N - 1 : 0;
   static const int xcd = knob("PFB_FIR_LDS_XCD") ? std::atoi(knob("PFB_FIR_LDS_XCD")) : 1;
+  if (a.din) {
+    if (a.z) return hipErrorInvalidValue;
+    auto go = [&](auto in) -> hipError_t {
+      using IN = decltype(in);
+      if (a.variant == kBunton)
+        return launch_kernel(fir_lds_dada_kernel<PW, DE, NU, kBunton, IN>, grid, dim3(NT), 0, s, a, (int)ranges, cs,
+                             xcd);
+      return launch_kernel(fir_lds_dada_kernel<PW, DE, NU, kPadded, IN>, grid, dim3(NT), 0, s, a, (int)ranges, cs,
+                           xcd);
+    };
+    return a.din_nbit == 8 ? go(InDada8{}) : a.din_nbit == 16 ? go(InDada16{}) : go(InDada32{});
+  }
   // (launch_kernel: timed by the profiler's armed events like every other single launch)
   if (a.variant == kBunton)
     return launch_kernel(fir_lds_kernel<PW, DE, NU, kBunton>, grid, dim3(NT), 0, s, a, (int)ranges, cs, xcd);
@@ -623,21 +662,30 @@ static hipError_t launch_fir_window_t(const AnalysisArgs& a, hipStream_t s) {
   return go(std::integral_constant<int, 3>{});
 }
 
+// the LDS-shared form where NU divides the workgroup (8/7, 4/3); PFB_FIR_LDS=0: A/B
+static bool fir_lds_shape(const AnalysisArgs& a, int de) {
+  static const bool no_lds = knob("PFB_FIR_LDS") && std::atoi(knob("PFB_FIR_LDS")) == 0;
+  if (de != 7 && de != 3) return false;
+  const int NU = de == 7 ? 8 : 4;
+  return !no_lds && a.nu == NU && a.N % (NT / NU) == 0;
+}
+
 // register-window FIR if the shape has an instance (window PW >= P, DE | exact M)
 template <int DE>
 static bool launch_fir_window_de(const AnalysisArgs& a, hipStream_t s, hipError_t* e) {
   if (a.P > 32 || a.P < DE) return false;
-  // the LDS-shared form where NU divides the workgroup (8/7, 4/3); PFB_FIR_LDS=0: A/B
-  static const bool no_lds = knob("PFB_FIR_LDS") && std::atoi(knob("PFB_FIR_LDS")) == 0;
   if constexpr (DE == 7 || DE == 3) {
-    constexpr int NU = DE == 7 ? 8 : 4;
-    if (!no_lds && a.nu == NU && a.N % (NT / NU) == 0) {
+    if (fir_lds_shape(a, DE)) {
       if (a.P <= 13) *e = launch_fir_lds_t<13, DE>(a, s);
       else if (a.P <= 16) *e = launch_fir_lds_t<16, DE>(a, s);
       else if (a.P <= 25) *e = launch_fir_lds_t<25, DE>(a, s);
       else *e = launch_fir_lds_t<32, DE>(a, s);
       return true;
     }
+  }
+  if (a.din) {  // (fir_window_kernel reads packed cf32 only: analysis_reads_dada)
+    *e = hipErrorInvalidValue;
+    return true;
   }
   if (a.P <= 13) *e = launch_fir_window_t<13, DE>(a, s);
   else if (a.P <= 16) *e = launch_fir_window_t<16, DE>(a, s);
@@ -698,6 +746,13 @@ static hipError_t launch_stream(const AnalysisArgs& a, hipStream_t s) {
               : a.out_rs == 1 && a.sel_n == 0 ? analysis_stream_kernel<N, P, NU, DE, 0, false, 2>
               : a.out_rs > 0                  ? analysis_stream_kernel<N, P, NU, DE, 0, false, 1>
                                               : analysis_stream_kernel<N, P, NU, DE, 0>;
+  if (a.din) {
+    // a DADA section read in place: the plain channelised product only
+    if (a.z || a.out_rs != 0) return hipErrorInvalidValue;
+    kern = a.din_nbit == 8    ? analysis_stream_dada_kernel<N, P, NU, DE, LCBF, InDada8>
+           : a.din_nbit == 16 ? analysis_stream_dada_kernel<N, P, NU, DE, LCBF, InDada16>
+                              : analysis_stream_dada_kernel<N, P, NU, DE, LCBF, InDada32>;
+  }
   // channel-major stores go out in row pairs: the launch's rows must start and end even
   if (!LCBF && !a.z && a.out_rs == 1 && a.sel_n == 0 && ((a.row0 & 1) || (a.K & 1))) return hipErrorInvalidValue;
   // the carry (pre) is read only in each workgroup's first WIN-row window prologue: every
@@ -718,7 +773,10 @@ static hipError_t launch_stream(const AnalysisArgs& a, hipStream_t s) {
   int64_t wgs = std::min<int64_t>(n_steps, per_pol);
   // a workgroup's rows (its steps' NEW rows each + the WIN-row window) must fit one
   // buffer descriptor: huge single series get more, shorter ranges
-  const int64_t fit_steps = (kRsrcMaxBytes / (8 * N) - SH::WIN) / SH::NEW;
+  // (bytes from one sample of a series to its next: 8, or a DADA section's n_pol x 2 x NBIT / 8)
+  const int64_t sstep = a.din ? (int64_t)a.n_pol * (a.din_nbit / 4) : 8;
+  const int64_t fit_steps = (kRsrcMaxBytes / (sstep * N) - SH::WIN) / SH::NEW;
+  if (fit_steps <= 0) return hipErrorInvalidValue;
   wgs = std::max(wgs, (n_steps + fit_steps - 1) / fit_steps);
   // (PFB_ANA_STEPS=S: S steps per workgroup, ceil(n_steps / S) workgroups instead of the
   // resident count; PFB_ANA_LINEAR=1: linear workgroup order — experiments A/B)
@@ -830,6 +888,16 @@ bool analysis_fused_takes_carry(const AnalysisArgs& a) {
          knob("PFB_FUSED_NO_CARRY") == nullptr;
 }
 
+bool analysis_reads_dada(const AnalysisArgs& a, int nbit) {
+  if (nbit != 8 && nbit != 16 && nbit != 32) return false;
+  // (one workgroup's rows must fit a descriptor at n_pol x 2 x NBIT / 8 bytes per sample)
+  if ((int64_t)a.n_pol * (nbit / 4) * a.N * 512 > kRsrcMaxBytes) return false;
+  if (stream_shape(a)) return knob("PFB_ANALYSIS_NO_STREAM") == nullptr;
+  bool fused = false;
+  if (!analysis_supported(a.N, a.P, a.variant, &fused) || fused || !fir_window_applies(a)) return false;
+  return fir_lds_shape(a, (int)((int64_t)a.M * a.nu / a.N));
+}
+
 bool analysis_takes_offset(const AnalysisArgs& a) {
   return stream_shape(a) && knob("PFB_ANALYSIS_NO_STREAM") == nullptr;
 }
@@ -851,6 +919,7 @@ hipError_t launch_analysis(const AnalysisArgs& a, hipStream_t s) {
     const bool generic_ok = !fused && a.zblk == 2 && a.z_row0 == 0 && fir_window_applies(a);
     if (!stream_ok && !generic_ok) return hipErrorInvalidValue;
   }
+  if (a.din && (!analysis_reads_dada(a, a.din_nbit) || a.z)) return hipErrorInvalidValue;
   static const bool no_stream = knob("PFB_ANALYSIS_NO_STREAM") != nullptr;
   if (fused && stream_shape(a) && !no_stream) {
     static const int mask = knob("PFB_ANA_MASK") ? std::atoi(knob("PFB_ANA_MASK")) : 0;

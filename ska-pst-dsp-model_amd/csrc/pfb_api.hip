@@ -238,6 +238,7 @@ struct pfb_analysis_plan {
   DevBuf carry, work, stage_in, stage_out;
   DevBuf carry_next;  // device streams: the streaming kernel writes the next carry here, then swap
   int64_t buffered = 0;
+  int last_dada = PFB_DADA_INPUT_NONE;  // pfb_analysis_last_dada_input
   // round trip (pfb_roundtrip_execute): the analysis runs on this stream, ahead of the
   // synthesis on the caller's stream; one event per chunk orders them
   hipStream_t aux = nullptr;
@@ -268,19 +269,35 @@ struct CarryOut {
   int64_t src, n, dst_ps;
 };
 
+// A single-channel DADA section (TFP, NDIM 2, NBIT 8 / 16 / 32, aligned to a complex sample)
+// the analysis kernel reads in place instead of `in` (pfb_analysis_execute_dada, FUSED)
+struct AnaDada {
+  const void* base;
+  int nbit;
+};
+
+// dd: the launch reads the section instead of `in` (analysis_dada_fusable plans only)
 static pfb_status analysis_run(pfb_analysis_plan* p, const float2* in, int64_t in_ps, int64_t n_dat,
                                float2* out, int64_t out_ps, int64_t row0, int64_t K_end,
                                int64_t K_total, hipStream_t s, float2* z = nullptr,
                                int64_t z_ps = 0, int64_t z_row0 = 0, int64_t pad = 0,
                                const OutLayout* lay = nullptr, int zblk = 0, const float2* pre = nullptr,
-                               int z_stage = 0, const CarryOut* co = nullptr) {
+                               int z_stage = 0, const CarryOut* co = nullptr, const AnaDada* dd = nullptr) {
   if (K_end <= row0) return PFB_OK;
+  if (dd) p->last_dada = PFB_DADA_INPUT_FUSED;
+  const double in_b = dd ? 2.0 * (dd->nbit / 8) : 8.0;  // bytes per input sample
   if (p->variant == pfb::kLowCbf) {
     pfb::LowCbfArgs l{};
     l.in = in;
     l.in_pol_stride = in_ps;
     l.n_dat = n_dat;
-    l.pad = p->lowcbf_pad ? 1536 : 0;
+    // (a DADA stream call: the carried samples in front of the section, pad = their count)
+    l.pad = pre ? pad : p->lowcbf_pad ? 1536 : 0;
+    l.pre = pre;
+    if (dd) {
+      l.din = dd->base;
+      l.din_nbit = dd->nbit;
+    }
     l.out = out;
     l.out_pol_stride = out_ps;
     l.K = K_end;
@@ -288,7 +305,7 @@ static pfb_status analysis_run(pfb_analysis_plan* p, const float2* in, int64_t i
     l.taps = p->taps.as<float>();
     l.tw = p->twN.as<float2>();
     l.scale = 4096.0f;  // 2^9 * 2048 * 256 / 2^9 / 128
-    ProfScope ps(0, (double)p->n_pol * (8.0 * n_dat + 8.0 * K_end * p->C), s);
+    ProfScope ps(0, (double)p->n_pol * (in_b * n_dat + 8.0 * K_end * p->C), s);
     HIPCHK(pfb::launch_lowcbf(l, s));
     return PFB_OK;
   }
@@ -300,6 +317,10 @@ static pfb_status analysis_run(pfb_analysis_plan* p, const float2* in, int64_t i
     a.carry_src = co->src;
     a.carry_n = co->n;
     a.carry_pol_stride = co->dst_ps;
+  }
+  if (dd) {
+    a.din = dd->base;
+    a.din_nbit = dd->nbit;
   }
   a.scratch = nullptr;
   if (!p->fused && !z) {
@@ -313,7 +334,7 @@ static pfb_status analysis_run(pfb_analysis_plan* p, const float2* in, int64_t i
                                  : (K_end - row0) * p->M + (K_end == K_total ? n_dat - K_total * p->M : 0);
   // (with z: the stage-1 rows are a synthesis intermediate, not algorithmic bytes —
   // the synthesis' algorithmic read of its input is counted by the block kernel)
-  const double bytes = (double)p->n_pol * (8.0 * in_samples + 8.0 * (K_end - row0) * p->N);
+  const double bytes = (double)p->n_pol * (in_b * in_samples + 8.0 * (K_end - row0) * p->N);
   // generic path = FIR + row FFT launches (z_stage 1 / 2: one of them, timed as its own
   // class; their bytes: the FIR reads the input and writes the stage-1 rows, the row FFT
   // reads them and writes the channelised product)
@@ -322,6 +343,12 @@ static pfb_status analysis_run(pfb_analysis_plan* p, const float2* in, int64_t i
   const double cls_bytes = z_stage == 1 ? (double)p->n_pol * 8.0 * in_samples + zrow_bytes
                            : z_stage == 2 ? 2.0 * zrow_bytes : bytes;
   ProfScope ps(cls, cls_bytes, s, p->fused || z_stage != 0);
+  if (dd && !p->fused) {
+    // the FIR of the N > 256 path reads the section: timed alone as class 4, which names it
+    ProfScope fir(4, (double)p->n_pol * in_b * in_samples + zrow_bytes, s);
+    HIPCHK(pfb::launch_analysis(a, s));
+    return PFB_OK;
+  }
   HIPCHK(pfb::launch_analysis(a, s));
   return PFB_OK;
 }
@@ -376,6 +403,26 @@ static bool analysis_offset_ok(const pfb_analysis_plan* p) {
   a.P = p->P;
   a.nu = p->nu;
   return pfb::analysis_takes_offset(a);
+}
+
+// FUSED (pfb_api.h): the plan's kernel loads such a section itself
+static bool analysis_dada_fusable(const pfb_analysis_plan* p, const void* base, int nbit, int ndim, int order) {
+  if (ndim != 2 || order != PFB_DADA_TFP || (nbit != 8 && nbit != 16 && nbit != 32)) return false;
+  if (reinterpret_cast<uintptr_t>(base) % (size_t)(nbit / 4) != 0) return false;
+  pfb::AnalysisArgs a{};
+  a.variant = p->variant;
+  a.N = p->N;
+  a.M = p->M;
+  a.P = p->P;
+  a.nu = p->nu;
+  a.n_pol = p->n_pol;
+  if (p->variant == pfb::kLowCbf) {
+    // (the streaming kernel's LCBF instantiation, unless the experiments build's knob picks
+    // the one-shot kernel: pfb_lowcbf.hip)
+    if (pfb::knob("PFB_LOWCBF_STREAM") && std::atoi(pfb::knob("PFB_LOWCBF_STREAM")) == 0) return false;
+    a.variant = pfb::kBunton;
+  }
+  return pfb::analysis_reads_dada(a, nbit);
 }
 
 static bool analysis_fused_carry_ok(const pfb_analysis_plan* p) {
@@ -573,26 +620,74 @@ int64_t pfb_analysis_output_length(const pfb_analysis_plan* p, int64_t n_dat) {
   return analysis_K(p, n_dat);
 }
 
-pfb_status pfb_analysis_execute(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps,
-                                int64_t n_dat, pfb_cf32* out, int64_t out_ps, int64_t cap,
-                                int64_t* n_out, int32_t mem, void* stream) {
+// A DADA data section as the input of an analysis call (pfb_analysis_execute_dada,
+// pfb_filterbank_execute_dada): n samples x 1 channel x the plan's n_pol x ndim values of nbit
+struct AnaSection {
+  const void* base;
+  int nbit, ndim, order;
+};
+
+static pfb_status ana_section_check(const pfb_analysis_plan* p, const AnaSection& sec, int64_t n) {
+  if (!p) return fail(PFB_ERR_INVALID_ARG, "null plan");
+  if (sec.nbit != 8 && sec.nbit != 16 && sec.nbit != 32 && sec.nbit != 64)
+    return fail(PFB_ERR_INVALID_ARG, "NBIT must be 8, 16, 32 or 64");
+  if (sec.ndim != 1 && sec.ndim != 2) return fail(PFB_ERR_INVALID_ARG, "NDIM must be 1 or 2");
+  if (sec.order != PFB_DADA_TFP && sec.order != PFB_DADA_LOWCBF)
+    return fail(PFB_ERR_INVALID_ARG, "unknown sample order");
+  if (sec.order == PFB_DADA_LOWCBF && n > 0 && n % 32)
+    return fail(PFB_ERR_INVALID_ARG, "LowCBF data are heaps of 32 samples");
+  return PFB_OK;
+}
+
+// STAGED: samples [t0, t0 + n) of the section unpacked to dst[pol][0, n) (pfb_dada_unpack; a
+// LowCBF section from a heap boundary only)
+static pfb_status ana_section_unpack(const pfb_analysis_plan* p, const AnaSection& sec, int64_t t0, int64_t n,
+                                     float2* dst, int64_t dps, hipStream_t s) {
+  if (n <= 0) return PFB_OK;
+  const char* src = static_cast<const char*>(sec.base) + t0 * p->n_pol * sec.ndim * (sec.nbit / 8);
+  return pfb_dada_unpack(src, sec.nbit, sec.ndim, sec.order, n, 1, p->n_pol, reinterpret_cast<pfb_cf32*>(dst), dps,
+                         s);
+}
+
+// pfb_analysis_execute; sec: the series are a DADA section (device memory) instead of `in`
+static pfb_status analysis_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps, const AnaSection* sec,
+                                int64_t n_dat, pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
+                                int32_t mem, void* stream) {
+  if (sec) in = static_cast<const pfb_cf32*>(sec->base);
   if (!p || (!in && n_dat > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
   if (n_dat < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_dat");
   HIPCHK(hipSetDevice(p->device));
+  p->last_dada = PFB_DADA_INPUT_NONE;
   hipStream_t s = (hipStream_t)stream;
   const int64_t K = analysis_K(p, n_dat);
   PadConsume pad_once{&p->lowcbf_pad};
   if (n_out) *n_out = K;
   if (K == 0) {
     pad_once.accept();
+    // (no launch: the path the section's rows would have taken)
+    if (sec)
+      p->last_dada = analysis_dada_fusable(p, sec->base, sec->nbit, sec->ndim, sec->order) ? PFB_DADA_INPUT_FUSED
+                                                                                         : PFB_DADA_INPUT_STAGED;
     return PFB_OK;
   }
   if (!out) return fail(PFB_ERR_INVALID_ARG, "null output");
   if (cap < K) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld rows",
                            (long long)cap, (long long)K);
-  if (mem == PFB_MEM_DEVICE && (in_ps < n_dat || out_ps < K * p->C))
+  if (mem == PFB_MEM_DEVICE && ((!sec && in_ps < n_dat) || out_ps < K * p->C))
     return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
   pad_once.accept();
+  if (sec) {
+    if (analysis_dada_fusable(p, sec->base, sec->nbit, sec->ndim, sec->order)) {
+      const AnaDada dd{sec->base, sec->nbit};
+      return analysis_run(p, nullptr, 0, n_dat, (float2*)out, out_ps, 0, K, K, s, nullptr, 0, 0, 0, nullptr, 0,
+                          nullptr, 0, nullptr, &dd);
+    }
+    HIPCHK(p->stage_in.ensure((size_t)p->n_pol * n_dat * sizeof(float2)));
+    p->last_dada = PFB_DADA_INPUT_STAGED;
+    const pfb_status st = ana_section_unpack(p, *sec, 0, n_dat, p->stage_in.as<float2>(), n_dat, s);
+    if (st != PFB_OK) return st;
+    return analysis_run(p, p->stage_in.as<float2>(), n_dat, n_dat, (float2*)out, out_ps, 0, K, K, s);
+  }
   if (mem == PFB_MEM_DEVICE) {
     return analysis_run(p, (const float2*)in, in_ps, n_dat, (float2*)out, out_ps, 0, K, K, s);
   }
@@ -610,9 +705,35 @@ pfb_status pfb_analysis_execute(pfb_analysis_plan* p, const pfb_cf32* in, int64_
   return PFB_OK;
 }
 
+pfb_status pfb_analysis_execute(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps,
+                                int64_t n_dat, pfb_cf32* out, int64_t out_ps, int64_t cap,
+                                int64_t* n_out, int32_t mem, void* stream) {
+  return analysis_exec(p, in, in_ps, nullptr, n_dat, out, out_ps, cap, n_out, mem, stream);
+}
+
+pfb_status pfb_analysis_execute_dada(pfb_analysis_plan* p, const void* in, int32_t nbit, int32_t ndim,
+                                     int32_t order, int64_t n_dat, pfb_cf32* out, int64_t out_ps, int64_t cap,
+                                     int64_t* n_out, void* stream) {
+  const AnaSection sec{in, nbit, ndim, order};
+  const pfb_status st = ana_section_check(p, sec, n_dat);
+  if (st != PFB_OK) return st;
+  return analysis_exec(p, nullptr, 0, &sec, n_dat, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream);
+}
+
+int32_t pfb_analysis_last_dada_input(const pfb_analysis_plan* p) { return p ? p->last_dada : -1; }
+
 static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps, int64_t n_in,
                                   pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out, int32_t mem,
-                                  void* stream, const OutLayout* lay);
+                                  void* stream, const OutLayout* lay, const AnaSection* sec = nullptr);
+
+pfb_status pfb_filterbank_execute_dada(pfb_analysis_plan* p, const void* in, int32_t nbit, int32_t ndim,
+                                       int32_t order, int64_t n_in, pfb_cf32* out, int64_t out_ps, int64_t cap,
+                                       int64_t* n_out, void* stream) {
+  const AnaSection sec{in, nbit, ndim, order};
+  const pfb_status st = ana_section_check(p, sec, n_in);
+  if (st != PFB_OK) return st;
+  return filterbank_exec(p, nullptr, 0, n_in, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream, nullptr, &sec);
+}
 
 pfb_status pfb_filterbank_execute(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps,
                                   int64_t n_in, pfb_cf32* out, int64_t out_ps, int64_t cap,
@@ -671,13 +792,25 @@ pfb_status pfb_filterbank_execute_strided(pfb_analysis_plan* p, const pfb_cf32* 
 
 }  // extern "C"
 
+// sec: the new samples are a DADA section (device memory) instead of `in`.  The carry stays
+// packed cf32, so cf32 and DADA calls may alternate on one plan.
 static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps, int64_t n_in,
                                   pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out, int32_t mem,
-                                  void* stream, const OutLayout* lay) {
+                                  void* stream, const OutLayout* lay, const AnaSection* sec) {
+  if (sec) {
+    in = static_cast<const pfb_cf32*>(sec->base);
+    in_ps = n_in;
+  }
   if (!p || (!in && n_in > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
   if (n_in < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_in");
   HIPCHK(hipSetDevice(p->device));
   hipStream_t s = (hipStream_t)stream;
+  // FUSED: the kernel reads the section's new samples in place; STAGED: they are unpacked
+  // behind the carry in the concatenation buffer and the cf32 path runs
+  const bool fus = sec && analysis_dada_fusable(p, sec->base, sec->nbit, sec->ndim, sec->order);
+  const AnaDada dd_{sec ? sec->base : nullptr, sec ? sec->nbit : 0};
+  const AnaDada* dd = fus ? &dd_ : nullptr;
+  const int last_dada = !sec ? PFB_DADA_INPUT_NONE : PFB_DADA_INPUT_STAGED;  // (a fused launch sets FUSED)
   const int64_t total = p->buffered + n_in;
   const hipMemcpyKind kin = mem == PFB_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   if (mem == PFB_MEM_DEVICE) {
@@ -700,11 +833,17 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
     const int64_t Kt = K - (K % p->nu);
     const int64_t input_idat = (Kt * p->N * p->de) / p->nu;
     static const bool no_split = pfb::knob("PFB_FB_NO_SPLIT") != nullptr;  // A/B
-    if (!no_split && mem == PFB_MEM_DEVICE && B > 0 && p->variant == pfb::kBunton && analysis_offset_ok(p) &&
-        input_idat >= B && p->lowcbf_pad == false) {
+    // (a DADA section: the one-launch form below only, else staged; a fused LowCBF stream
+    // call takes it too — its cf32 call concatenates)
+    const int64_t win_ = ((int64_t)p->de * (16 / p->nu) + p->P) * p->N;
+    const bool lcbf_dd = dd && p->variant == pfb::kLowCbf;
+    if (!no_split && mem == PFB_MEM_DEVICE && B > 0 &&
+        ((p->variant == pfb::kBunton && analysis_offset_ok(p)) || lcbf_dd) && input_idat >= B &&
+        p->lowcbf_pad == false && (!sec || (fus && B <= win_))) {
       if (n_out) *n_out = Kt;
       if (Kt > cap) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld rows",
                                 (long long)cap, (long long)Kt);
+      p->last_dada = last_dada;
       const int64_t M = p->M, PN = (int64_t)p->P * p->N;
       // the streaming kernel's register window: DE (16 / NU) new rows per step + P (its first
       // window holds every carried sample a workgroup's rows read when B fits in it —
@@ -724,9 +863,15 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
           HIPCHK(p->carry_next.ensure((size_t)p->n_pol * nb * sizeof(float2)));
           co.dst = p->carry_next.as<float2>();
         }
+        // (the LowCBF instantiation has no carry copy: unpacked by a launch behind it)
         pfb_status st = analysis_run(p, (const float2*)in, in_ps, n_in, (float2*)out, out_ps, 0, Kt, K, s,
-                                     nullptr, 0, 0, B, lay, 0, p->carry.as<float2>(), 0, nb > 0 ? &co : nullptr);
+                                     nullptr, 0, 0, B, lay, 0, p->carry.as<float2>(), 0,
+                                     nb > 0 && !lcbf_dd ? &co : nullptr, dd);
         if (st != PFB_OK) return st;
+        if (lcbf_dd) {
+          st = ana_section_unpack(p, *sec, input_idat - B, nb, co.dst, nb, s);
+          if (st != PFB_OK) return st;
+        }
         if (nb > 0) std::swap(p->carry, p->carry_next);
         p->buffered = std::max<int64_t>(nb, 0);
         return PFB_OK;
@@ -771,8 +916,9 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
     // take the streaming kernel above — goes straight to `out`: the launch stores the shifted
     // rows below Kt through the layout and drops rows [Kt, K), so there are no scratch rows
     // and no staging buffer)
-    if (mem == PFB_MEM_DEVICE && B > 0 && !p->lowcbf_pad && p->fused && analysis_fused_carry_ok(p) &&
+    if (!sec && mem == PFB_MEM_DEVICE && B > 0 && !p->lowcbf_pad && p->fused && analysis_fused_carry_ok(p) &&
         input_idat >= B && Kt > 0) {
+      p->last_dada = last_dada;
       if (n_out) *n_out = Kt;
       if (Kt > cap) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld rows",
                                 (long long)cap, (long long)Kt);
@@ -808,15 +954,23 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
   // the input already on the device the kernels read it in place (no copy)
   const float2* w;
   int64_t wps;
-  if (p->buffered == 0 && mem == PFB_MEM_DEVICE) {
-    w = (const float2*)in;
+  const bool in_place = p->buffered == 0 && mem == PFB_MEM_DEVICE && (!sec || fus);
+  if (in_place) {
+    w = (const float2*)in;  // (a fused section: read through dd, `w` is not dereferenced)
     wps = in_ps;
   } else {
+    dd = nullptr;
     HIPCHK(p->work.ensure((size_t)p->n_pol * std::max<int64_t>(total, 1) * sizeof(float2)));
     float2* wk = p->work.as<float2>();
     HIPCHK(copy_pols(wk, total, p->carry.as<float2>(), p->buffered, p->buffered, p->n_pol,
                      hipMemcpyDeviceToDevice, s));
-    HIPCHK(copy_pols(wk + p->buffered, total, (const float2*)in, in_ps, n_in, p->n_pol, kin, s));
+    if (sec) {
+      // (unpacked straight behind the carry: no second copy)
+      const pfb_status st = ana_section_unpack(p, *sec, 0, n_in, wk + p->buffered, total, s);
+      if (st != PFB_OK) return st;
+    } else {
+      HIPCHK(copy_pols(wk + p->buffered, total, (const float2*)in, in_ps, n_in, p->n_pol, kin, s));
+    }
     w = wk;
     wps = total;
   }
@@ -827,6 +981,7 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
   if (Kt > cap) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld rows",
                             (long long)cap, (long long)Kt);
   pad_once.accept();
+  p->last_dada = dd ? PFB_DADA_INPUT_FUSED : last_dada;
   if (Kt > 0) {
     // rows are independent except for the padded variant's circular shift over all K
     // rows: the others compute just the Kt kept rows, straight into the caller's buffer
@@ -854,7 +1009,8 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
         dps = Krun * p->C;
       }
     }
-    pfb_status st = analysis_run(p, w, wps, total, dst, dps, 0, Krun, K, s, nullptr, 0, 0, 0, lay);
+    pfb_status st = analysis_run(p, w, wps, total, dst, dps, 0, Krun, K, s, nullptr, 0, 0, 0, lay, 0, nullptr, 0,
+                                 nullptr, dd);
     if (st != PFB_OK) return st;
     if (dst != (float2*)out) {
       const hipMemcpyKind ko = mem == PFB_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
@@ -867,8 +1023,14 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
   if (nb > 0) {
     HIPCHK(p->carry.ensure((size_t)p->n_pol * nb * sizeof(float2)));
     // carry may alias nothing in `work` (separate buffer); copy per pol
-    HIPCHK(copy_pols(p->carry.as<float2>(), nb, w + input_idat, wps, nb, p->n_pol,
-                     hipMemcpyDeviceToDevice, s));
+    if (dd) {
+      // (the section's tail, unpacked: the carry stays packed cf32)
+      const pfb_status st = ana_section_unpack(p, *sec, input_idat, nb, p->carry.as<float2>(), nb, s);
+      if (st != PFB_OK) return st;
+    } else {
+      HIPCHK(copy_pols(p->carry.as<float2>(), nb, w + input_idat, wps, nb, p->n_pol,
+                       hipMemcpyDeviceToDevice, s));
+    }
   }
   p->buffered = std::max<int64_t>(nb, 0);
   if (mem == PFB_MEM_HOST) HIPCHK(hipStreamSynchronize(s));

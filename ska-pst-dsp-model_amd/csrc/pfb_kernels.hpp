@@ -101,7 +101,17 @@ struct AnalysisArgs {
   // padded plans with out_rs > 0: the rows kept of the K_total computed (the stream object's
   // nu-trimmed T_out, FilterBank.m:93-104); shifted rows [out_keep, K_total) are not stored
   int64_t out_keep = 0;
+  // The input is a single-channel DADA section read in place instead of `in`
+  // (pfb_analysis_execute_dada; analysis_reads_dada): TFP order, NDIM 2, din_nbit 8 / 16
+  // (integers) or 32 (float), sample t of polarisation p at byte (t n_pol + p) din_nbit / 4 of
+  // din, which is aligned to one complex sample.  n_dat, pad, pre and carry_src count samples
+  // as ever; `in` and in_pol_stride are unused.
+  const void* din = nullptr;
+  int din_nbit = 0;
 };
+// the plan's kernel has a loader for such a section (the streaming kernel; the LDS-shared FIR
+// of the N > 256 path, launches without stage-1 rows)
+bool analysis_reads_dada(const AnalysisArgs& a, int nbit);
 // SKA-Low CBF PST filterbank through the streaming analysis kernel (pfb_analysis.hip)
 hipError_t launch_lowcbf_stream(const AnalysisArgs& a, hipStream_t s);
 // analysis kernels that can also emit the synthesis stage-1 rows (see AnalysisArgs::z)
@@ -260,6 +270,12 @@ struct LowCbfArgs {
   const float* taps;       // 3072 taps (device)
   const float2* tw;        // e^{-2 pi i m / 256}
   float scale;             // 2^28 / 2^9 / 128 = 2^12
+  // a stream object's carried samples in front of `in` (AnalysisArgs::pre, with pad = their
+  // count; a DADA stream call — the cf32 one concatenates)
+  const float2* pre = nullptr;
+  // the input is a DADA section read in place (AnalysisArgs::din; streaming path only)
+  const void* din = nullptr;
+  int din_nbit = 0;
 };
 hipError_t launch_lowcbf(const LowCbfArgs& a, hipStream_t s);
 

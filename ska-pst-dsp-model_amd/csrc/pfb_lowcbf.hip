@@ -148,8 +148,14 @@ hipError_t launch_lowcbf(const LowCbfArgs& a, hipStream_t s) {
     b.twN = a.tw;
     b.pad = a.pad;
     b.lcbf_scale = a.scale;
+    b.pre = a.pre;
+    b.pre_pol_stride = a.pad;
+    b.din = a.din;
+    b.din_nbit = a.din_nbit;
     return launch_lowcbf_stream(b, s);
   }
+  // (the one-shot kernel reads packed cf32 without a carry)
+  if (a.din || a.pre) return hipErrorInvalidValue;
   static_assert(NT == LN, "one thread per polyphase arm");
   const size_t bytes = ((size_t)LROWS * lds_row(LN) + tw_slots(LN)) * sizeof(float2);
   hipError_t e = set_lds(lowcbf_kernel, bytes);

@@ -127,6 +127,11 @@ SYMBOLS = [
                                                       c_int64, c_void_p, c_int64, c_int64,
                                                       POINTER(c_int64), c_void_p]),
     ("pfb_synthesis_last_dada_input", c_int32, [c_void_p]),
+    ("pfb_analysis_execute_dada", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64,
+                                            c_void_p, c_int64, c_int64, POINTER(c_int64), c_void_p]),
+    ("pfb_filterbank_execute_dada", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64,
+                                              c_void_p, c_int64, c_int64, POINTER(c_int64), c_void_p]),
+    ("pfb_analysis_last_dada_input", c_int32, [c_void_p]),
     ("pfb_synthesis_execute_strided", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
                                                 c_int64, c_int64, c_void_p, c_int64, c_int64,
                                                 POINTER(c_int64), c_void_p]),

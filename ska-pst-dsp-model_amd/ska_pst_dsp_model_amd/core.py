@@ -220,6 +220,43 @@ class AnalysisPlan:
                       mem, stream))
         return out[:, :n_out.value, :]
 
+    def execute_dada(self, raw, nbit: int, ndim: int = 2, lowcbf: bool = False, stateful: bool = False):
+        """The analysis of a single-channel DADA data section (``raw``: a device tensor of
+        bytes or samples, n_dat x n_pol x ndim values of nbit in TFP or LowCBF order, the
+        polarisations interleaved as the file holds them) — bit for bit
+        ``execute(layout.dada_unpack(raw, nbit, ndim, 1, n_pol)[:, :, 0])``, without the
+        unpacked series crossing HBM where the analysis kernel can load the section itself
+        (pfb_analysis_execute_dada / pfb_filterbank_execute_dada; ``last_dada_input()``
+        tells).  n_dat is inferred as ``layout.dada_unpack`` does.  Returns the
+        (n_pol, K, n_chan) buffer like ``execute``."""
+        if not is_device_array(raw):
+            raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "execute_dada: expects a device tensor")
+        raw = raw.contiguous()
+        if int(nbit) not in (8, 16, 32, 64) or int(ndim) not in (1, 2):
+            n_dat = 0  # (the C ABI rejects the format)
+        else:
+            n_dat = (raw.numel() * raw.element_size()) // (self.n_pol * int(ndim) * (int(nbit) // 8))
+            if lowcbf:
+                n_dat -= n_dat % 32
+        if stateful:
+            cap = (self.buffered_samples + n_dat) // max(self.step, 1) + 1
+        else:
+            cap = self.output_length(n_dat)
+        out = self._alloc_out(raw, True, cap)
+        n_out = c_int64(0)
+        order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
+        fn = self._lib.pfb_filterbank_execute_dada if stateful else self._lib.pfb_analysis_execute_dada
+        _lib.check(fn(self._h, c_void_p(raw.data_ptr()), int(nbit), int(ndim), order, n_dat,
+                      c_void_p(out.data_ptr()), cap * self.out_chan, cap, byref(n_out), _stream_of(raw, self)))
+        return out[:, :n_out.value, :]
+
+    def last_dada_input(self) -> str:
+        """How the plan's last DADA call read its section: 'fused' (the analysis kernel
+        loaded the file's own bytes), 'staged' (unpacked first), 'none' (no DADA call, or a
+        cf32 call since) — pfb_analysis_last_dada_input."""
+        m = int(self._lib.pfb_analysis_last_dada_input(self._h))
+        return {_lib.PFB_DADA_INPUT_FUSED: "fused", _lib.PFB_DADA_INPUT_STAGED: "staged"}.get(m, "none")
+
 
 # ============================================================================ synthesis
 def _resolve_taper(taper, nf: int, ov: int, spectral_length: int = 0):

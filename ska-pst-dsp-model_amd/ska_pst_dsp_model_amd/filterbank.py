@@ -124,6 +124,22 @@ class FilterBank(Channelizer):
         view = out.transpose(1, 2) if is_device_array(out) else out.transpose(0, 2, 1)
         return self, view
 
+    def execute_dada(self, raw, nbit: int, ndim: int = 2, n_pol: int = 1):
+        """``execute`` of the next chunk as the file holds it: ``raw`` is a device tensor of
+        a single-channel DADA section's bytes (``DADARead.generate_raw``), ``n_pol``
+        polarisations interleaved (TFP).  Same output and carry as
+        ``execute(DADARead.generate(...)[:, 0, :])``, bit for bit
+        (``AnalysisPlan.execute_dada``).  With ``rndInput`` set the section is unpacked and
+        takes ``execute``: the quantiser's scale needs the variance of the whole input."""
+        if self.rndInput:
+            x = layout.dada_unpack(raw, nbit, ndim, 1, int(n_pol))[:, :, 0]
+            return self.execute(x)
+        plan = self._ensure_plan(int(n_pol))
+        out = plan.execute_dada(raw, nbit, ndim=ndim, stateful=True)  # (n_pol, T_out, n_chan)
+        if self.rndOutput:
+            out = _quantize(out, self.rmsOutput, self.device)
+        return self, out.transpose(1, 2)
+
     def reset(self):
         if self._plan is not None:
             self._plan.reset()

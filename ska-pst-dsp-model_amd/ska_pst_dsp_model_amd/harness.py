@@ -22,7 +22,8 @@ import numpy as np
 
 from . import dada
 from .config import as_rational
-from .core import polyphase_analysis, polyphase_analysis_padded, synthesis_plan
+from .core import (_pfc_view, analysis_plan, polyphase_analysis, polyphase_analysis_padded,
+                   synthesis_plan)
 from .firio import read_fir_filter_coeff
 from .window import PFBWindow
 
@@ -65,7 +66,10 @@ def channelize(input_data_file_path: str, channels: int = None, os_factor_str: s
     os_factor = as_rational(str(os_factor_str))
     output_base = f"channelize.{channels}.{'-'.join(str(os_factor_str).split('/'))}"
     _, _, output_file_name = create_output_file_names(output_file_name, output_base)
-    data, hdr = dada.read_dada_file(input_data_file_path, device)
+    raw, hdr = dada.read_dada_raw(input_data_file_path, device)
+    if hdr.get("INSTRUMENT") == "LowCBF":
+        raise ValueError("channelize: LowCBF files are read with DADARead "
+                         "(read_dada_file.m has no heap reordering)")
     taps = read_fir_filter_coeff(fir_filter_path)
     ch = dict(hdr)
     tsamp = float(hdr.get("TSAMP", "1"))
@@ -74,8 +78,16 @@ def channelize(input_data_file_path: str, channels: int = None, os_factor_str: s
     ch["NCHAN_PFB_0"] = str(int(channels))
     ch["OS_FACTOR"] = f"{os_factor.nu}/{os_factor.de}"
     dada.add_fir_filter_to_header(ch, taps, os_factor)
-    fn = polyphase_analysis_padded if use_padded else polyphase_analysis
-    chan = fn(data[:, 0, :], taps, int(channels), os_factor)  # (n_pol, channels, K)
+    if int(hdr["NCHAN"]) == 1:
+        # the analysis reads the single-channel section's own bytes (no unpacked copy)
+        name = "polyphase_analysis_padded" if use_padded else "polyphase_analysis"
+        plan = analysis_plan(taps, int(channels), os_factor, name, int(hdr["NPOL"]), raw.device.index or 0)
+        chan = _pfc_view(plan.execute_dada(raw, int(hdr["NBIT"]), ndim=int(hdr["NDIM"])))  # (n_pol, channels, K)
+    else:
+        # (channel 1 of a channelised file: unpacked, as read_dada_file does)
+        data = dada._matlab_view(dada._unpack(raw, hdr, False))
+        fn = polyphase_analysis_padded if use_padded else polyphase_analysis
+        chan = fn(data[:, 0, :], taps, int(channels), os_factor)  # (n_pol, channels, K)
     path = os.path.join(output_dir, output_file_name)
     dada.write_dada_file(path, chan, ch)
     return dada.DADAFile(path, device).load_data()
