@@ -823,82 +823,57 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
       return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
   }
   {
-    // Carry without the concatenation copy (streaming analysis kernel, device input):
-    // rows k >= ceil(B / M) read only the new input, so they run on it in place with the
-    // carried B samples as a read offset (AnalysisArgs::pad); the few rows before that run
-    // on a small stitched buffer of the carry and the head of the input.  The result is the
-    // same per row as the concatenated run (same kernel, same samples).
+    // Carry without the concatenation copy (streaming analysis kernel, device input): when
+    // the new carry starts in the new input (input_idat >= B), ONE launch reads the new
+    // input in place with the carried B samples as a read offset (AnalysisArgs::pad), and
+    // the carried samples themselves through a second descriptor in its first register
+    // window (AnalysisArgs::pre).  The result is the same per row as the concatenated run
+    // (same kernel, same samples).
     const int64_t B = p->buffered;
     const int64_t K = analysis_K(p, total);
     const int64_t Kt = K - (K % p->nu);
     const int64_t input_idat = (Kt * p->N * p->de) / p->nu;
     static const bool no_split = pfb::knob("PFB_FB_NO_SPLIT") != nullptr;  // A/B
-    // (a DADA section: the one-launch form below only, else staged; a fused LowCBF stream
-    // call takes it too — its cf32 call concatenates)
-    const int64_t win_ = ((int64_t)p->de * (16 / p->nu) + p->P) * p->N;
+    // the streaming kernel's register window: DE (16 / NU) new rows per step + P (its first
+    // window holds every carried sample a workgroup's rows read when B fits in it —
+    // launch_stream checks the same bound).  A stream call leaves at most P N + NU M - 1
+    // samples behind (total - Kt M with K - Kt < NU), which is below the window's
+    // P N + 16 M for every NU <= 16: every carry this object makes fits
+    // (tests/test_stream_model.py enumerates it); a longer one would concatenate below.
+    const int64_t win = ((int64_t)p->de * (16 / p->nu) + p->P) * p->N;
+    // (a DADA section: fused only, else staged; a fused LowCBF stream call takes this path
+    // too — its cf32 call concatenates)
     const bool lcbf_dd = dd && p->variant == pfb::kLowCbf;
-    if (!no_split && mem == PFB_MEM_DEVICE && B > 0 &&
+    if (!no_split && mem == PFB_MEM_DEVICE && B > 0 && B <= win &&
         ((p->variant == pfb::kBunton && analysis_offset_ok(p)) || lcbf_dd) && input_idat >= B &&
-        p->lowcbf_pad == false && (!sec || (fus && B <= win_))) {
+        p->lowcbf_pad == false && (!sec || fus)) {
       if (n_out) *n_out = Kt;
       if (Kt > cap) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld rows",
                                 (long long)cap, (long long)Kt);
       p->last_dada = last_dada;
-      const int64_t M = p->M, PN = (int64_t)p->P * p->N;
-      // the streaming kernel's register window: DE (16 / NU) new rows per step + P (its first
-      // window holds every carried sample a workgroup's rows read when B fits in it —
-      // launch_stream checks the same bound)
-      const int64_t win = ((int64_t)p->de * (16 / p->nu) + p->P) * p->N;
-      if (B <= win) {
-        // ONE launch: the streaming kernel reads the carried samples through a second
-        // descriptor in its first window (AnalysisArgs::pre) — no stitched rows, no copies
-        // before it; then the new carry (stream order: after the kernel read the old one).
-        // (Round 5: the bound was P N; a cascade's stage-2 carry of up to P N + NU M samples
-        // per series then took the stitched path — two copies and a small launch per call.)
-        // (round 5) the kernel also copies the next carry into the second carry buffer —
-        // no copy launch after it — and the two buffers swap
-        const int64_t nb = total - input_idat;
-        CarryOut co{nullptr, input_idat - B, nb, nb};
-        if (nb > 0) {
-          HIPCHK(p->carry_next.ensure((size_t)p->n_pol * nb * sizeof(float2)));
-          co.dst = p->carry_next.as<float2>();
-        }
-        // (the LowCBF instantiation has no carry copy: unpacked by a launch behind it)
-        pfb_status st = analysis_run(p, (const float2*)in, in_ps, n_in, (float2*)out, out_ps, 0, Kt, K, s,
-                                     nullptr, 0, 0, B, lay, 0, p->carry.as<float2>(), 0,
-                                     nb > 0 && !lcbf_dd ? &co : nullptr, dd);
-        if (st != PFB_OK) return st;
-        if (lcbf_dd) {
-          st = ana_section_unpack(p, *sec, input_idat - B, nb, co.dst, nb, s);
-          if (st != PFB_OK) return st;
-        }
-        if (nb > 0) std::swap(p->carry, p->carry_next);
-        p->buffered = std::max<int64_t>(nb, 0);
-        return PFB_OK;
-      }
-      // (even: a channel-major strided launch stores row pairs; Kt is a multiple of nu)
-      const int64_t k_split = std::min(Kt, (((B + M - 1) / M) + 1) & ~(int64_t)1);
-      if (k_split > 0) {
-        const int64_t L = std::min(total, (k_split - 1) * M + PN);
-        HIPCHK(p->work.ensure((size_t)p->n_pol * L * sizeof(float2)));
-        float2* wk = p->work.as<float2>();
-        HIPCHK(copy_pols(wk, L, p->carry.as<float2>(), B, std::min(B, L), p->n_pol, hipMemcpyDeviceToDevice, s));
-        if (L > B) HIPCHK(copy_pols(wk + B, L, (const float2*)in, in_ps, L - B, p->n_pol, hipMemcpyDeviceToDevice, s));
-        pfb_status st = analysis_run(p, wk, L, L, (float2*)out, out_ps, 0, k_split, K, s, nullptr, 0, 0, 0, lay);
-        if (st != PFB_OK) return st;
-      }
-      if (Kt > k_split) {
-        pfb_status st = analysis_run(p, (const float2*)in, in_ps, n_in, (float2*)out, out_ps, k_split, Kt, K, s,
-                                     nullptr, 0, 0, B, lay);
-        if (st != PFB_OK) return st;
-      }
-      // carry = input(:, :, input_idat + 1 : end): all of it lies in the new input
+      // no stitched rows, no copies before the launch; then the new carry (stream order:
+      // after the kernel read the old one).
+      // (Round 5: the bound was P N; a cascade's stage-2 carry of up to P N + NU M samples
+      // per series then took a stitched two-launch path — two copies and a small launch per
+      // call.)
+      // (round 5) the kernel also copies the next carry into the second carry buffer —
+      // no copy launch after it — and the two buffers swap
       const int64_t nb = total - input_idat;
+      CarryOut co{nullptr, input_idat - B, nb, nb};
       if (nb > 0) {
-        HIPCHK(p->carry.ensure((size_t)p->n_pol * nb * sizeof(float2)));
-        HIPCHK(copy_pols(p->carry.as<float2>(), nb, (const float2*)in + (input_idat - B), in_ps, nb, p->n_pol,
-                         hipMemcpyDeviceToDevice, s));
+        HIPCHK(p->carry_next.ensure((size_t)p->n_pol * nb * sizeof(float2)));
+        co.dst = p->carry_next.as<float2>();
       }
+      // (the LowCBF instantiation has no carry copy: unpacked by a launch behind it)
+      pfb_status st = analysis_run(p, (const float2*)in, in_ps, n_in, (float2*)out, out_ps, 0, Kt, K, s,
+                                   nullptr, 0, 0, B, lay, 0, p->carry.as<float2>(), 0,
+                                   nb > 0 && !lcbf_dd ? &co : nullptr, dd);
+      if (st != PFB_OK) return st;
+      if (lcbf_dd) {
+        st = ana_section_unpack(p, *sec, input_idat - B, nb, co.dst, nb, s);
+        if (st != PFB_OK) return st;
+      }
+      if (nb > 0) std::swap(p->carry, p->carry_next);
       p->buffered = std::max<int64_t>(nb, 0);
       return PFB_OK;
     }

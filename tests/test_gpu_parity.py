@@ -418,11 +418,14 @@ def test_filterbank_stream_equals_one_shot(gpu):
 
 @pytest.mark.parametrize("os_,tpc", [("8/7", 12), ("4/3", 12), ("8/7", 11)])
 def test_filterbank_stream_carry_in_place(gpu, os_, tpc):
-    """Streaming FilterBank on the 256-channel streaming kernel with carried samples: the
-    rows that read only the new input run on it in place (the carry as a read offset),
-    the first ones on a small stitched buffer (pfb_filterbank_execute).  Chunks include
-    ones shorter than the carry (the concatenating path) and two polarisations; the
-    result equals the one-shot analysis bit for bit and the streaming oracle at 1e-6."""
+    """Streaming FilterBank on the 256-channel streaming kernel with carried samples: one
+    launch reads the new input in place (the carry length as a read offset) and the carried
+    samples through the kernel's second descriptor (pfb_filterbank_execute; there is no
+    stitched two-launch path: no stream state carries more than the kernel's first window,
+    tests/test_stream_model.py).  Chunks include ones shorter than the carry (the
+    concatenating path) and two polarisations; the result equals the one-shot analysis bit
+    for bit and the streaming oracle at 1e-6.  The boundaries of each path's predicate are
+    in tests/test_gpu_stream_edges.py."""
     import torch
     pfb = _pfb()
     taps = pfb.design_PFB_FIR_filter(256, os_, tpc)

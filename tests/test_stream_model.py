@@ -1,0 +1,266 @@
+"""CPU checks of tests/stream_model.py, the integer restatement of filterbank_exec and ifb_exec
+(ska-pst-dsp-model_amd/csrc/pfb_api.hip):
+
+  * it reproduces what the GPU suite already asserts of the real plans (the carries of
+    test_gpu_strided_synthesis.py, the DADA paths of test_gpu_dada_analysis.py);
+  * no stream state carries more than the streaming kernel's first window — the bound under
+    which filterbank_exec has no stitched two-launch path;
+  * every sequence table of tests/test_gpu_stream_edges.py hits every edge it claims, so a table
+    that drifts off its edge fails here instead of silently testing less.
+"""
+import pytest
+
+import stream_model as sm
+
+
+# ----------------------------------------------------------------------------- reproductions
+def test_model_reproduces_strided_synthesis_stream():
+    """test_gpu_strided_synthesis.test_stream_chunks_match_packed_stream: rows (384, 32, 224, 672)
+    at sample_offset 5 leave carries [224, 256, 160, 192], read in_place / staged / staged /
+    in_place, the second call returning nothing."""
+    recs = sm.synthesis_stream(sm.C2_SYNTH[5], (384, 32, 224, 672), "strided")
+    assert [r.carry_after for r in recs] == [224, 256, 160, 192]
+    assert [sm.synthesis_diag(r)[0] for r in recs] == ["in_place", "staged", "staged", "in_place"]
+    assert [r.rows > 0 for r in recs] == [True, False, True, True]
+    assert [r.path for r in recs] == ["in_place", "concat", "split(2, 2)", "split(1, 4)"]
+
+
+def test_model_reproduces_dada_synthesis_stream():
+    """test_gpu_dada_synthesis: the five LowCBF chunks and the three odd TFP ones."""
+    recs = sm.synthesis_stream(sm.C2_SYNTH[5], (384, 32, 224, 672, 288), "dada")
+    assert [sm.synthesis_diag(r)[1] for r in recs] == ["fused", "staged", "staged", "fused", "staged"]
+    assert [r.carry_after for r in recs] == [224, 256, 160, 192, 160]
+    recs = sm.synthesis_stream(sm.C2_SYNTH[5], (333, 199, 501), "dada")
+    assert [sm.synthesis_diag(r)[1] for r in recs] == ["fused", "staged", "fused"]
+    assert [r.carry_after for r in recs] == [176, 216, 240]
+
+
+@pytest.mark.parametrize("shape", [sm.STREAM_SHAPES["8over7-p13"], sm.LOWCBF_SHAPE], ids=["c2", "lowcbf"])
+def test_model_reproduces_dada_analysis_stream(shape):
+    """test_gpu_dada_analysis.CHUNKS: chunk 2 (100 samples after a carry) completes no row and is
+    unpacked behind the carry; every other call reads its section in place."""
+    chunks = (9000, 100, 7777, 6001, 9001)
+    recs = sm.analysis_stream(shape, chunks, "dada_fused")
+    assert [sm.analysis_dada_diag(r) for r in recs] == ["fused", "staged", "fused", "fused", "fused"]
+    assert [r.path for r in recs] == ["in_place", "concat", "one_launch", "one_launch", "one_launch"]
+    mixed = sm.analysis_stream(shape, chunks, ["dada_fused", "packed"] * 2 + ["dada_fused"])
+    assert [sm.analysis_dada_diag(r) for r in mixed] == ["fused", "none", "fused", "none", "fused"]
+    assert sum(r.rows for r in recs) > 64 and recs[-1].carry_after > 0
+
+
+def test_model_lowcbf_pad_is_consumed_by_a_rowless_call():
+    """analysis_K adds the 1536 pre-pad while it is due; the first accepted call consumes it even
+    when it returns no rows (pfb_api.hip: PadConsume::accept before the Kt > 0 branch)."""
+    s = sm.LOWCBF_SHAPE
+    assert sm.analysis_K(s, 1000, True) == 0 and sm.analysis_K(s, 1536 + 192, True) == 1
+    recs = sm.analysis_stream(s, (1000, 2072))
+    assert recs[0].pad_due and not recs[1].pad_due
+    # 3072 samples without the pad: no row yet (with it, (3072 + 1536 - 3072) / 192 = 8)
+    assert recs[1].K == 0 and recs[1].carry_after == 3072
+    again = sm.analysis_stream(s, (1000, "reset", 3072))
+    assert again[1].pad_due and again[1].rows == 8
+
+
+# ----------------------------------------------------------------------------- reachability
+SHAPES = dict(sm.STREAM_SHAPES, lowcbf=sm.LOWCBF_SHAPE)
+# (maximum reachable carry, one-launch window)
+EXPECTED_MAXIMA = {"8over7-p13": (5119, 6912), "8over7-p12": (4863, 6656), "4over3-p13": (4095, 6400),
+                   "4over3-p12": (3839, 6144), "lowcbf": (3839, 6144)}
+
+
+@pytest.mark.parametrize("name", sorted(SHAPES))
+def test_no_reachable_carry_exceeds_the_one_launch_window(name):
+    """Breadth-first over every n_in in [0, P N + 3 nu M) from an empty object: the largest carry
+    is P N + nu M - 1, below the window P N + 16 M.  filterbank_exec relies on it: a carried
+    length above the window has no path of its own (it would concatenate)."""
+    s = SHAPES[name]
+    seen = sm.reachable_carries(s)
+    print(f"{name}: {len(seen)} reachable carries, max {max(seen)}, window {s.window}")
+    assert (max(seen), s.window) == EXPECTED_MAXIMA[name]
+    assert max(seen) == s.max_carry < s.window
+    assert min(seen) == 0
+    # the search's premise: a call's new carry depends on B and n_in only through B + n_in
+    for B in sorted(seen)[::97]:
+        for n in (0, 1, s.M - 1, s.PN, s.PN + s.nu * s.M + 5):
+            assert (sm.analysis_call(s, B, n)[0].carry_after
+                    == sm.analysis_call(s, 0, B + n)[0].carry_after), (B, n)
+
+
+# ----------------------------------------------------------------------------- the tables
+def _flags(recs):
+    out = set()
+    for r in recs:
+        out |= r.flags
+    return out
+
+
+def _analysis_tables():
+    t = []
+    for name, s in sm.STREAM_SHAPES.items():
+        t.append((f"bunton-main-{name}", s, sm.bunton_main_chunks(s), sm.BUNTON_MAIN_EDGES))
+        t.append((f"bunton-short-{name}", s, sm.BUNTON_SHORT_CHUNKS, sm.BUNTON_SHORT_EDGES))
+    t.append(("lowcbf", sm.LOWCBF_SHAPE, sm.LOWCBF_CHUNKS, sm.LOWCBF_EDGES))
+    t.append(("padded-fused", sm.PADDED_FUSED_SHAPE, sm.PADDED_FUSED_CHUNKS, sm.PADDED_FUSED_EDGES))
+    t.append(("padded-generic", sm.PADDED_GENERIC_SHAPE, sm.PADDED_GENERIC_CHUNKS, sm.PADDED_GENERIC_EDGES))
+    return t
+
+
+@pytest.mark.parametrize("table", _analysis_tables(), ids=lambda t: t[0])
+def test_analysis_table_hits_its_edges(table):
+    name, shape, chunks, edges = table
+    # (a fused LowCBF section takes the one-launch path; cf32 LowCBF calls concatenate)
+    entry = "dada_fused" if shape.variant == sm.LOWCBF else "packed"
+    recs = sm.analysis_stream(shape, chunks, entry)
+    print(name, chunks)
+    print(sm.describe(recs))
+    missing = set(edges) - _flags(recs)
+    assert not missing, f"{name} no longer hits {sorted(missing)}"
+    assert all(r.carry_after <= shape.max_carry < shape.window for r in recs)
+    assert sum(r.rows for r in recs) > 0
+
+
+def test_bunton_main_table_is_the_stated_one():
+    s = sm.STREAM_SHAPES["8over7-p13"]
+    assert sm.bunton_main_chunks(s) == (5376, 3328, 1791, 1, 0, 3584, 3327, 1, 255, 1, 1, 20000)
+    recs = sm.analysis_stream(s, sm.bunton_main_chunks(s))
+    # carry 3584 then 3328 samples: the new carry starts at the first new sample
+    assert (recs[1].carry_before, recs[1].input_idat, recs[1].path) == (3584, 3584, "one_launch")
+    # 5119 carried then 1 sample: 8 rows out of the concatenation
+    assert (recs[3].carry_before, recs[3].rows, recs[3].path) == (5119, 8, "concat")
+    assert (recs[4].n_in, recs[4].carry_before) == (0, 3328)
+    assert (recs[11].carry_before, recs[11].pad, recs[11].path) == (3329, 3329, "one_launch")
+    for name, shape in sm.STREAM_SHAPES.items():
+        r = sm.analysis_stream(shape, sm.bunton_main_chunks(shape))
+        assert r[2].carry_after == r[3].carry_before == shape.max_carry, name
+        assert r[3].n_in == 1 and r[3].rows == shape.nu and r[3].input_idat < r[3].carry_before, name
+        assert r[1].input_idat == r[1].carry_before and r[1].path == "one_launch", name
+
+
+@pytest.mark.parametrize("name", sorted(sm.STREAM_SHAPES))
+def test_bunton_short_table_reads_short_carries_through_pre(name):
+    s = sm.STREAM_SHAPES[name]
+    recs = sm.analysis_stream(s, sm.BUNTON_SHORT_CHUNKS)
+    pads = tuple(r.pad for r in recs if r.path == "one_launch")
+    assert pads == sm.BUNTON_SHORT_PADS and all(p < s.PN for p in pads)
+
+
+def test_lowcbf_table_lands_on_its_carries():
+    recs = sm.analysis_stream(sm.LOWCBF_SHAPE, sm.LOWCBF_CHUNKS, "dada_fused")
+    assert (recs[0].rows, recs[0].pad_due, recs[0].carry_after) == (0, True, 1000)
+    assert recs[1].carry_after == 3072 and recs[2].carry_after == sm.LOWCBF_SHAPE.max_carry == 3839
+    assert (recs[3].n_in, recs[3].rows) == (1, 4)
+    assert recs[4].path == "one_launch" and recs[4].input_idat == recs[4].carry_before == 3072
+    assert recs[6].pad_due and recs[6].carry_before == 0 and recs[6].rows == 20  # after reset()
+    cf32 = sm.analysis_stream(sm.LOWCBF_SHAPE, sm.LOWCBF_CHUNKS, "packed")
+    assert {r.path for r in cf32} == {"in_place", "concat"}
+
+
+def test_padded_tables_land_on_their_carries():
+    recs = sm.analysis_stream(sm.PADDED_FUSED_SHAPE, sm.PADDED_FUSED_CHUNKS)
+    assert [r.carry_after for r in recs] == [0, 1, 9, 111, 0, 5, 18, 18, 10]
+    assert [r.path for r in recs] == ["in_place", "in_place", "fused_pre", "fused_pre", "fused_pre", "in_place",
+                                      "concat", "concat", "fused_pre"]
+    assert (recs[4].n_in, recs[4].carry_before, recs[4].rows) == (1, 111, 8)
+    assert recs[5].n_in < sm.PADDED_FUSED_SHAPE.M
+    gen = sm.analysis_stream(sm.PADDED_GENERIC_SHAPE, sm.PADDED_GENERIC_CHUNKS)
+    assert {r.path for r in gen} == {"in_place", "concat"}
+    assert [r.carry_after for r in gen][:5] == [0, 1, 9, 191, 0]
+    # the call after an empty new carry reads in place
+    for rs in (recs, gen):
+        for a, b in zip(rs, rs[1:]):
+            if "empty_new_carry" in a.flags:
+                assert b.path == "in_place"
+
+
+SYNTH_TABLES = [(f"{k}-offset{so}", shapes[so], rows[so], edges[so])
+                for k, shapes, rows, edges in (("c2", sm.C2_SYNTH, sm.C2_SYNTH_ROWS, sm.C2_SYNTH_EDGES),
+                                               ("small", sm.SMALL_SYNTH, sm.SMALL_SYNTH_ROWS,
+                                                sm.SMALL_SYNTH_EDGES))
+                for so in (0, 5)]
+
+
+@pytest.mark.parametrize("table", SYNTH_TABLES, ids=lambda t: t[0])
+def test_synthesis_table_hits_its_edges(table):
+    name, shape, rows, edges = table
+    recs = sm.synthesis_stream(shape, rows)
+    print(name, rows)
+    print(sm.describe(recs))
+    missing = set(edges) - _flags(recs)
+    assert not missing, f"{name} no longer hits {sorted(missing)}"
+    rejected = [r for r in recs if r.path == "rejected"]
+    assert len(rejected) == 1 and rejected[0].n_in == 3
+    assert rejected[0].carry_after == rejected[0].carry_before > 0
+    if shape.sample_offset == 0:
+        # every block stitched, the in-place range empty
+        eq = [r for r in recs if "idat_eq_carry" in r.flags]
+        assert eq and all(r.b_s == r.blocks > 0 and r.path.startswith("split") for r in eq)
+    else:
+        lt = [r for r in recs if "olen_lt_full" in r.flags]
+        assert lt and all(r.path.startswith("split") and "rounded_carry" in r.flags and 0 < r.rows < r.full
+                          for r in lt)
+
+
+def test_c2_synthesis_tables_are_the_stated_ones():
+    r0 = sm.synthesis_stream(sm.C2_SYNTH[0], sm.C2_SYNTH_ROWS[0])
+    assert (r0[5].carry_before, r0[5].n_in, r0[5].path) == (160, 96, "split(1, 1)")
+    r5 = sm.synthesis_stream(sm.C2_SYNTH[5], sm.C2_SYNTH_ROWS[5])
+    assert [r.carry_after for r in r5[:4]] == [224, 256, 160, 192]
+    assert (r5[7].n_in, r5[7].path, r5[7].rows, r5[7].full) == (165, "split(2, 2)", 71008, 71680)
+
+
+def test_rotations_cover_every_entry_at_every_call():
+    ent = ("a", "b", "c", "d")
+    rots = sm.rotations(ent)
+    assert len(rots) == 4
+    for i in range(11):
+        assert {r[i % 4] for r in rots} == set(ent)
+
+
+# ----------------------------------------------------------------------------- model vs oracle
+# The model restates the C ABI; the float64 oracle objects restate FilterBank.m and
+# InverseFilterBank.m.  Rows and carries must agree call by call on every table (random taps of
+# the right length: only the counts matter here, the values are compared on the GPU).
+def _oracle_analysis_counts(shape, chunks, variant):
+    import numpy as np
+    from oracle import pfb_oracle as orc
+    rng = np.random.default_rng(7)
+    n_taps = 3072 if shape.variant == sm.LOWCBF else (shape.P - 1) * shape.N + 1
+    taps = rng.standard_normal(n_taps) / shape.N
+    os_ = f"{shape.nu}/{shape.de}"
+    ofb = orc.FilterBankOracle(taps, shape.N, os_, variant)
+    out = []
+    for n in chunks:
+        if n == "reset":
+            ofb = orc.FilterBankOracle(taps, shape.N, os_, variant)
+            continue
+        y = ofb.execute((rng.standard_normal((1, 1, n)) + 0j).astype(np.complex64))
+        out.append((y.shape[2], int(ofb.buffered_samples)))
+    return out
+
+
+@pytest.mark.parametrize("table", _analysis_tables(), ids=lambda t: t[0])
+def test_analysis_model_agrees_with_the_oracle_object(table):
+    name, shape, chunks, _ = table
+    variant = {sm.BUNTON: "polyphase_analysis", sm.PADDED: "polyphase_analysis_padded",
+               sm.LOWCBF: "polyphase_analysis_lowcbf"}[shape.variant]
+    recs = sm.analysis_stream(shape, chunks)
+    assert [(r.rows, r.carry_after) for r in recs] == _oracle_analysis_counts(shape, chunks, variant)
+
+
+@pytest.mark.parametrize("table", SYNTH_TABLES, ids=lambda t: t[0])
+def test_synthesis_model_agrees_with_the_oracle_object(table):
+    import numpy as np
+    from oracle import pfb_oracle as orc
+    name, shape, rows, _ = table
+    rng = np.random.default_rng(8)
+    o = orc.InverseFilterBankOracle(np.ones(1), shape.N, f"{shape.nu}/{shape.de}", shape.Nf, shape.Ov, "tukey",
+                                    sample_offset=shape.sample_offset)
+    got = []
+    for n in rows:
+        x = (rng.standard_normal((1, shape.N, n)) + 1j * rng.standard_normal((1, shape.N, n)))
+        try:
+            got.append((o.execute(x).shape[2], int(o.buffered_samples)))
+        except ValueError:
+            got.append("rejected")
+    recs = sm.synthesis_stream(shape, rows)
+    assert got == ["rejected" if r.path == "rejected" else (r.rows, r.carry_after) for r in recs]
