@@ -408,6 +408,66 @@ pfb_status pfb_filterbank_execute_dada(pfb_analysis_plan* plan, const void* in, 
                                        void* stream);
 int32_t pfb_analysis_last_dada_input(const pfb_analysis_plan* plan);
 
+/* Analysis writing its product straight into a DADA data section (polyphase_analysis /
+ * FilterBank.m:65-128 followed by write_dada_data.m:32-50): TFP order, NDIM 2, out_nbit 8 /
+ * 16 (integers), 32 (float) or 64 (double).  Device memory only.  Element (row k, channel c,
+ * polarisation p) of the section, with C = pfb_analysis_output_channels and P the plan's
+ * n_pol, lies at byte ((k * C + c) * P + p) * 2 * out_nbit / 8 of `out`, re then im.  The
+ * bytes written, *n_out, the status codes, pfb_filterbank_buffered,
+ * pfb_filterbank_output_rows and the stream state are those of the corresponding cf32-output
+ * call (pfb_analysis_execute, pfb_filterbank_execute and their _dada twins) into a packed
+ * [pol][k][c] buffer, both components multiplied by out_scale in float32, followed by
+ * pfb_dada_pack at out_nbit, bit for bit: the same float32 operations in the same order.
+ * Exactly rows [0, *n_out) of the section are written and not one byte beyond; the rows a
+ * stream call trims to a multiple of the oversampling numerator and the spare rows of the
+ * padded variant have no place in `out`.  Every check runs before any launch or state change:
+ * a rejected stream call leaves the carry and the buffered count untouched, and a rejected
+ * call on a PFB_ANALYSIS_LOWCBF plan leaves the first-call pre-padding pending.
+ * PFB_ERR_INVALID_ARG: a null plan, null buffers when samples are given or rows are due,
+ * out_nbit not 8/16/32/64, a non-finite out_scale, `out` not aligned to one value of out_nbit,
+ * and the input-side conditions of the corresponding call.  PFB_ERR_BUFFER_TOO_SMALL, with
+ * nothing written: out_capacity_bytes below rows * C * P * 2 * out_nbit / 8.  cf32 and DADA
+ * input, and cf32 and DADA output stream calls may alternate on one plan: the carry stays
+ * packed cf32.
+ * FUSED: the analysis kernel converts and stores the samples itself, one range-checked buffer
+ * store of 2 / 4 / 8 bytes per complex sample, and the cf32 product never crosses HBM —
+ * out_nbit 8, 16 or 32, `out` aligned to one complex sample, and a plan on the streaming
+ * kernel (PFB_ANALYSIS_BUNTON with n_chan 256, os 8/7 or 4/3, 12 or 13 tap phases, and
+ * PFB_ANALYSIS_LOWCBF; stateless and stream calls).  The _dada_to_dada calls read the input
+ * section in place as well when it qualifies for pfb_analysis_execute_dada's FUSED and its
+ * nbit equals out_nbit or out_nbit is 32 (an integer file channelised into a float one); any
+ * other input section is unpacked into the plan's staging buffer first and the output stays
+ * fused (pfb_analysis_last_dada_input then reports STAGED).
+ * STAGED: every other plan (the padded variant with its circular row shift, n_chan other than
+ * 256, the FIR + row-FFT path), out_nbit 64 and an `out` aligned to a value but not to a
+ * complex sample run the cf32 path into a plan-owned buffer, then one scaled pack launch; so
+ * these calls accept every plan the cf32 calls accept.
+ * pfb_analysis_last_dada_output: which of the two the plan's last such call took, NONE before
+ * one or after a cf32-output call, -1 for a null plan.  (Measured A/B against the pair:
+ * DESIGN.md §4.7.) */
+typedef enum pfb_dada_output {
+  PFB_DADA_OUTPUT_NONE = 0,
+  PFB_DADA_OUTPUT_FUSED = 1,
+  PFB_DADA_OUTPUT_STAGED = 2
+} pfb_dada_output;
+pfb_status pfb_analysis_execute_to_dada(pfb_analysis_plan* plan, const pfb_cf32* in,
+                                        int64_t in_pol_stride, int64_t n_dat, void* out,
+                                        int32_t out_nbit, float out_scale, int64_t out_capacity_bytes,
+                                        int64_t* n_out, void* stream);
+pfb_status pfb_filterbank_execute_to_dada(pfb_analysis_plan* plan, const pfb_cf32* in,
+                                          int64_t in_pol_stride, int64_t n_in, void* out,
+                                          int32_t out_nbit, float out_scale, int64_t out_capacity_bytes,
+                                          int64_t* n_out, void* stream);
+pfb_status pfb_analysis_execute_dada_to_dada(pfb_analysis_plan* plan, const void* in, int32_t nbit,
+                                             int32_t ndim, int32_t order, int64_t n_dat, void* out,
+                                             int32_t out_nbit, float out_scale,
+                                             int64_t out_capacity_bytes, int64_t* n_out, void* stream);
+pfb_status pfb_filterbank_execute_dada_to_dada(pfb_analysis_plan* plan, const void* in, int32_t nbit,
+                                               int32_t ndim, int32_t order, int64_t n_in, void* out,
+                                               int32_t out_nbit, float out_scale,
+                                               int64_t out_capacity_bytes, int64_t* n_out, void* stream);
+int32_t pfb_analysis_last_dada_output(const pfb_analysis_plan* plan);
+
 /* The synthesis calls reading their channelised rows strided (device memory only): channel c
  * of row t of polarisation p is in[p * in_pol_stride + t * in_row_stride + c * in_chan_stride]
  * — the input-side mirror of pfb_filterbank_execute_strided.  Polarisations may interleave

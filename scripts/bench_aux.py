@@ -11,6 +11,9 @@ one MI355X, as algorithmic HBM bytes / time against the 8 TB/s peak.
   * --only-dada-analysis: analysis from a single-channel DADA section (C2, LowCBF, SKA-Mid
     stage 1), the staged pair (pfb_dada_unpack + pfb_analysis_execute) against
     pfb_analysis_execute_dada, interleaved
+  * --only-dada-output: analysis into a DADA section (C2, LowCBF, SKA-Mid stage 1), the pair
+    (execute, scale, pfb_dada_pack) against pfb_analysis_execute_to_dada /
+    pfb_analysis_execute_dada_to_dada, interleaved
   * --only-twostage-inverse: TwoStageInverseFilterBank with the channel gather against the
     strided input (pfb_inverse_filterbank_execute_strided), interleaved
 
@@ -58,6 +61,8 @@ def main():
                     help="the dada_synthesis A/B alone (--reps: calls per timed window)")
     ap.add_argument("--only-dada-analysis", action="store_true",
                     help="the dada_analysis A/B alone (--reps: calls per timed window)")
+    ap.add_argument("--only-dada-output", action="store_true",
+                    help="the dada_output A/B alone (--reps: calls per timed window)")
     ap.add_argument("--only-twostage-inverse", action="store_true",
                     help="the inverse cascade's gather vs strided-input A/B alone (--reps: calls per window)")
     ap.add_argument("--rounds", type=int, default=15,
@@ -96,6 +101,8 @@ def main():
         return dada_synthesis(torch, pfb, dev, max(args.reps, 20), args.rounds)
     if args.only_dada_analysis:
         return dada_analysis(torch, pfb, dev, max(args.reps, 20), args.rounds)
+    if args.only_dada_output:
+        return dada_output(torch, pfb, dev, max(args.reps, 20), args.rounds)
     if args.only_twostage_inverse:
         return twostage_inverse(torch, pfb, noise, max(args.reps, 20), max(args.rounds, 5))
     # ---- C2' (4/3) round trip
@@ -338,6 +345,119 @@ def dada_analysis(torch, pfb, dev, reps, rounds):
             "A_bytes": int(n_pol * (n * (esz + 8 + 8) + K * C * 8)),
             "B_bytes": int(n_pol * (n * esz + K * C * 8))}), flush=True)
         del plan, raw, x, out_a, out_b
+        torch.cuda.empty_cache()
+
+
+def dada_output(torch, pfb, dev, reps, rounds):
+    """Channelised product -> DADA section (TFP, NBIT 8 / 16 / 32).  A: the pair a caller had
+    before — the cf32-output call (pfb_analysis_execute, or pfb_analysis_execute_dada for a
+    DADA input), both components times the scale in float32 (one elementwise pass), then
+    pfb_dada_pack.  B: pfb_analysis_execute_to_dada / pfb_analysis_execute_dada_to_dada.  Both
+    through the C ABI into preallocated buffers.  The sections are asserted equal first; then
+    `rounds` windows of `reps` calls of each side, alternating A and B in one process, after a
+    warm-up of both.  One line per case with the median, min, max and quartiles of each side's
+    per-call time.  stays_fused: B's median lies below A's by more than the larger of the two
+    sides' interquartile spreads."""
+    from ctypes import byref, c_int64, c_void_p
+    from ska_pst_dsp_model_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator(device=dev).manual_seed(5)
+    taps87 = pfb.design_PFB_FIR_filter(256, "8/7", 12)
+    taps_pst = pfb.read_fir_filter_coeff(os.path.join(pfb.config.config_dir, "PST_filtertaps.txt"))
+    # (the SKA-Mid stage 1's tap count; the values do not bear on the time)
+    taps_mid = np.random.default_rng(4).standard_normal(4096 * 24 + 2049) / 4096
+    c2 = ("C2 256ch 8/7", taps87, 256, "8/7", "polyphase_analysis", 1 << 24)
+    # (shape..., input NBIT or 0 for cf32, output NBIT, n_pol)
+    cases = [c2 + (0, nbit, n_pol) for nbit in (8, 16, 32) for n_pol in (1, 2)]
+    cases += [c2 + (nbit, nbit, n_pol) for nbit in (16, 8) for n_pol in (1, 2)]
+    cases.append(("LowCBF PST filterbank", taps_pst, 256, "4/3", "polyphase_analysis_lowcbf", 1 << 24, 16, 16, 2))
+    cases.append(("SKA-Mid stage 1 4096ch 8/7 padded", taps_mid, 4096, "8/7", "polyphase_analysis_padded",
+                  1 << 26, 0, 16, 1))
+    dts = {8: torch.int8, 16: torch.int16, 32: torch.float32}
+    for shape, taps, N, os_, variant, n, in_nbit, nbit, n_pol in cases:
+        plan = pfb.AnalysisPlan(taps, N, os_, variant, n_pol)
+        if variant.endswith("lowcbf"):
+            plan.execute(torch.zeros((n_pol, 4096), dtype=torch.complex64, device=dev))  # the one-time padding
+        K, C = plan.output_length(n), plan.out_chan
+        if in_nbit:
+            lim = 1 << (in_nbit - 1)
+            src = torch.randint(-lim, lim, (n * n_pol * 2,), dtype=dts[in_nbit], device=dev, generator=g)
+        else:
+            src = torch.view_as_complex(torch.randn((n_pol, n, 2), device=dev, generator=g))
+        cf = torch.empty((n_pol, K, C), dtype=torch.complex64, device=dev)
+        scaled = torch.empty_like(cf)
+        sec_a = torch.empty((K, C, n_pol, 2), dtype=dts[nbit], device=dev)
+        sec_b = torch.empty_like(sec_a)
+        nbytes = sec_b.numel() * sec_b.element_size()
+        stream = c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        n_out = c_int64(0)
+
+        def execute_cf32():
+            if in_nbit:
+                _lib.check(lib.pfb_analysis_execute_dada(plan._h, c_void_p(src.data_ptr()), in_nbit, 2,
+                                                         _lib.PFB_DADA_TFP, n, c_void_p(cf.data_ptr()), K * C, K,
+                                                         byref(n_out), stream))
+            else:
+                _lib.check(lib.pfb_analysis_execute(plan._h, c_void_p(src.data_ptr()), n, n, c_void_p(cf.data_ptr()),
+                                                    K * C, K, byref(n_out), _lib.PFB_MEM_DEVICE, stream))
+
+        # the product's component rms at a third of the integer range (0.37 for NBIT 32)
+        execute_cf32()
+        rms = float(torch.view_as_real(cf).square().mean().sqrt())
+        scale = float(np.float32((((1 << (nbit - 1)) - 1) / 3.0 if nbit != 32 else 0.37) / rms))
+
+        def side_a():
+            execute_cf32()
+            torch.mul(torch.view_as_real(cf), scale, out=torch.view_as_real(scaled))
+            _lib.check(lib.pfb_dada_pack(c_void_p(scaled.data_ptr()), K * C, K, C, n_pol, c_void_p(sec_a.data_ptr()),
+                                         nbit, stream))
+
+        def side_b():
+            if in_nbit:
+                _lib.check(lib.pfb_analysis_execute_dada_to_dada(
+                    plan._h, c_void_p(src.data_ptr()), in_nbit, 2, _lib.PFB_DADA_TFP, n, c_void_p(sec_b.data_ptr()),
+                    nbit, scale, nbytes, byref(n_out), stream))
+            else:
+                _lib.check(lib.pfb_analysis_execute_to_dada(plan._h, c_void_p(src.data_ptr()), n, n,
+                                                            c_void_p(sec_b.data_ptr()), nbit, scale, nbytes,
+                                                            byref(n_out), stream))
+
+        side_a()
+        side_b()
+        path_in, path = plan.last_dada_input(), plan.last_dada_output()
+        torch.cuda.synchronize()
+        assert n_out.value == K and torch.equal(sec_a, sec_b), f"dada_output {shape} {in_nbit}->{nbit}: sections differ"
+        for _ in range(2):
+            timeit(torch, side_a, reps)
+            timeit(torch, side_b, reps)
+        ta, tb = [], []
+        for _ in range(rounds):
+            ta.append(timeit(torch, side_a, reps))
+            tb.append(timeit(torch, side_b, reps))
+
+        def stats(t):
+            q = np.percentile(t, [0, 25, 50, 75, 100])
+            return {k: round(float(v), 4) for k, v in zip(("min", "q25", "median", "q75", "max"), q)}
+        a, b = stats(ta), stats(tb)
+        iqr_a, iqr_b = a["q75"] - a["q25"], b["q75"] - b["q25"]
+        esz_in, esz = (2 * in_nbit // 8 if in_nbit else 8), 2 * nbit // 8
+        prod = K * C * 8
+        print(json.dumps({
+            "kernel": "dada_output", "shape": shape, "samples": n, "n_pol": n_pol,
+            "in": f"nbit{in_nbit}" if in_nbit else "cf32", "nbit": nbit, "path": path, "input_path": path_in,
+            "calls_per_window": reps, "windows": rounds, "outputs_equal": True,
+            "A_execute_scale_pack_ms": a, "B_execute_to_dada_ms": b,
+            "A_iqr_ms": round(iqr_a, 4), "B_iqr_ms": round(iqr_b, 4),
+            "A_spread_ms": round(a["max"] - a["min"], 4),
+            "B_below_A_by_ms": round(a["median"] - b["median"], 4),
+            "B_over_A": round(b["median"] / a["median"], 4),
+            "stays_fused": bool(path == "fused" and a["median"] - b["median"] > max(iqr_a, iqr_b)),
+            # A: the input, the product written, read and rewritten scaled, read again, the section
+            "A_bytes": int(n_pol * (n * esz_in + 4 * prod + K * C * esz)),
+            "A_bytes_without_scale_pass": int(n_pol * (n * esz_in + 2 * prod + K * C * esz)),
+            "B_bytes": int(n_pol * (n * esz_in + (K * C * esz if path == "fused" else 2 * prod + K * C * esz)))}),
+            flush=True)
+        del plan, src, cf, scaled, sec_a, sec_b
         torch.cuda.empty_cache()
 
 

@@ -2,6 +2,7 @@
 // analysis_stream_kernel (instantiated in pfb_analysis.hip).
 #pragma once
 #include "pfb_common.hpp"
+#include "pfb_sample.hpp"
 
 namespace pfb {
 
@@ -88,6 +89,71 @@ struct InDada8 {  // NBIT 8: int8 (re, im)
   }
 };
 
+// The store side of the same kernel (analysis_stream_body's OUT).  OutCf32: the packed
+// [pol][k][c] complex float32 rows (BufRowStore / LcbfRowStore and the strided stores).
+// OutDada8 / 16 / 32: a TFP DADA section, NDIM 2 (AnalysisArgs::dout) — kBytes per complex
+// sample, (re, im) converted by pfb_dada_pack's to_sample and written by one range-checked
+// buffer store (cache policy kAuxDadaOut).
+struct OutCf32 {
+  static constexpr bool kDada = false;
+};
+struct OutDada32 {  // NBIT 32: float (re, im)
+  static constexpr bool kDada = true;
+  static constexpr int kBytes = 8;
+  static __device__ __forceinline__ void store(__amdgpu_buffer_rsrc_t r, uint32_t off, float re, float im) {
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v2f{to_sample<float>(re), to_sample<float>(im)}),
+                                          r, off, 0, kAuxDadaOut);
+  }
+};
+struct OutDada16 {  // NBIT 16: int16 (re, im)
+  static constexpr bool kDada = true;
+  static constexpr int kBytes = 4;
+  static __device__ __forceinline__ void store(__amdgpu_buffer_rsrc_t r, uint32_t off, float re, float im) {
+    const uint32_t w = (uint32_t)(uint16_t)to_sample<int16_t>(re) | ((uint32_t)(uint16_t)to_sample<int16_t>(im) << 16);
+    __builtin_amdgcn_raw_buffer_store_b32(w, r, off, 0, kAuxDadaOut);
+  }
+};
+struct OutDada8 {  // NBIT 8: int8 (re, im)
+  static constexpr bool kDada = true;
+  static constexpr int kBytes = 2;
+  static __device__ __forceinline__ void store(__amdgpu_buffer_rsrc_t r, uint32_t off, float re, float im) {
+    const uint16_t w = (uint16_t)((uint16_t)(uint8_t)to_sample<int8_t>(re) | ((uint16_t)(uint8_t)to_sample<int8_t>(im) << 8));
+    __builtin_amdgcn_raw_buffer_store_b16(w, r, off, 0, kAuxDadaOut);
+  }
+};
+
+// Rows [k0, k0 + T) of a DADA section of C channels and P polarisations, polarisation `pol`
+// (BufRowStore's twin; LCBF: LcbfRowStore's bin -> channel map and drop rule, C = 216): FFT bin
+// f of row `row` is the complex sample at byte ((row C + c) P + pol) kBytes of the step's
+// first row, its value to_sample(oscale * (scale * v)) per component — the float32 products of
+// the cf32 store followed by the caller's scale and pfb_dada_pack, in that order.  The
+// descriptor covers the step's valid rows (all of both polarisations: a workgroup fills every
+// P-th sample); rows below `lo` and dropped bins are sent out of its range, rows at or above
+// the extent are dropped by the range check.  No branch around the store.
+template <class OUT, int N, bool LCBF>
+struct DadaRowStore {
+  static constexpr bool kIsLds = false;
+  static constexpr int C = LCBF ? 216 : N;
+  __amdgpu_buffer_rsrc_t r;
+  int lo, P, pol;
+  float scale, oscale;
+  __device__ __forceinline__ void store(int row, int f, float2 v) const {
+    const int c = LCBF ? ((f + 108) & 255) : f;
+    const bool ok = (row >= lo) & (c < C);
+    const uint32_t off = ok ? (uint32_t)(((row * C + c) * P + pol) * OUT::kBytes) : 0xFFFFFFF0u;
+    const float2 x = cscale(v, scale);
+    OUT::store(r, off, oscale * x.x, oscale * x.y);
+  }
+  __device__ __forceinline__ static DadaRowStore rows(void* base, int64_t k0, int T, int64_t k_lo, int64_t k_hi,
+                                                       int P, int pol, float scale, float oscale) {
+    const int64_t hi = min(max(k_hi - k0, (int64_t)0), (int64_t)T);
+    const int lo = (int)min(max(k_lo - k0, (int64_t)0), (int64_t)T);
+    const int64_t row_bytes = (int64_t)C * P * OUT::kBytes;
+    return DadaRowStore{make_rsrc_u(static_cast<char*>(base) + k0 * row_bytes, (uint32_t)(hi * row_bytes)), lo, P,
+                        pol, scale, oscale};
+  }
+};
+
 // ZOUT (round trip): each step's channelised rows are also inverse-transformed across
 // channels in LDS and written as synthesis stage-1 rows (AnalysisArgs::z), so the
 // synthesis does not re-read them from HBM.
@@ -129,8 +195,11 @@ struct SinkStore {
 // inside it are wave barriers (round 6; timing variants r06_v14: the FFT was 30 of the
 // kernel's 78 us with four workgroup barriers a step, memory traffic masked or not)
 // IN: the input fetch (InCf32, or a DADA section read in place)
-template <int N, int P, int NU, int DE, int ZOUT, bool LCBF, int GS, int TV = 0, class IN = InCf32>
+// OUT: the product's store (OutCf32, or a DADA section written in place: ZOUT 0, GS 0)
+template <int N, int P, int NU, int DE, int ZOUT, bool LCBF, int GS, int TV = 0, class IN = InCf32,
+          class OUT = OutCf32>
 __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int pol, int w, int nw) {
+  static_assert(!OUT::kDada || (ZOUT == 0 && GS == 0 && TV == 0), "the DADA store: the plain product only");
   using SH = StreamShape<N, P, NU, DE>;
   constexpr int M = SH::M, PE = SH::PE, QS = SH::QS, T = SH::T, NEW = SH::NEW, WIN = SH::WIN;
   constexpr bool kWR = (TV & 8) == 0 && wave_rows_ok<N, T, NT>();
@@ -309,6 +378,12 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
     });
     __syncthreads();
     if constexpr ((TV & 2) != 0) {
+    } else if constexpr (OUT::kDada) {
+      // the quantised product, straight into the caller's section (per-step descriptor, one
+      // always-issued store per complex sample, as the cf32 row stores)
+      const DadaRowStore<OUT, N, LCBF> st = DadaRowStore<OUT, N, LCBF>::rows(
+          a.dout, k0, T, a.row0, a.K, a.n_pol, pol, LCBF ? a.lcbf_scale : (float)N, a.dout_scale);
+      block_fft<N, -1, T, NT, kWR>(rows, st, rows, tw, c);
     } else if constexpr (LCBF) {
       const LcbfRowStore st = LcbfRowStore::rows(opol, k0, T, a.row0, a.K, a.lcbf_scale);
       block_fft<N, -1, T, NT, kWR>(rows, st, rows, tw, c);
@@ -379,6 +454,45 @@ template <int N, int P, int NU, int DE, bool LCBF, class IN>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void analysis_stream_dada_kernel(AnalysisArgs a) {
   const int w = a.linear ? (int)blockIdx.x : xcd_tile(blockIdx.x, gridDim.x);
   analysis_stream_body<N, P, NU, DE, 0, LCBF, 0, 0, IN>(a, blockIdx.y, w, gridDim.x);
+}
+
+// The same kernel storing its product as a DADA section (OUT: OutDada8 / 16 / 32;
+// AnalysisArgs::dout), from packed cf32 input or from a DADA section of the same NBIT read in
+// place.  A kernel of its own name again (pfb_ana_stream_dadaout.hip instantiates them).
+template <int N, int P, int NU, int DE, bool LCBF, class IN, class OUT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void analysis_stream_dadaout_kernel(AnalysisArgs a) {
+  const int w = a.linear ? (int)blockIdx.x : xcd_tile(blockIdx.x, gridDim.x);
+  analysis_stream_body<N, P, NU, DE, 0, LCBF, 0, 0, IN, OUT>(a, blockIdx.y, w, gridDim.x);
+}
+
+// Workgroups per polarisation of a streaming launch, each a contiguous range of steps
+struct StreamGrid {
+  int64_t n_steps, fit_steps, wgs;
+  int env_wpc;
+};
+template <class SH, int NU>
+inline hipError_t stream_grid(const AnalysisArgs& a, StreamGrid* g) {
+  constexpr int N = NT;
+  const int64_t q_lo = a.row0 / NU;
+  const int64_t n_steps = ((a.K + NU - 1) / NU - q_lo + SH::QS - 1) / SH::QS;
+  // LDS-limited resident workgroups per CU, each a contiguous range of steps
+  // two persistent workgroups per CU (one below the LDS-resident count of 3): longer step
+  // ranges amortise each workgroup's start-up window load; measured 4 % faster than 3
+  // (PFB_ANA_WG_PER_CU overrides, A/B knob)
+  int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / SH::lds_bytes));
+  static const int env_wpc = knob("PFB_ANA_WG_PER_CU") ? std::atoi(knob("PFB_ANA_WG_PER_CU")) : 0;
+  if (env_wpc > 0) per_cu = env_wpc;
+  const int64_t per_pol = std::max<int64_t>(1, (per_cu * cu_count()) / a.n_pol);
+  int64_t wgs = std::min<int64_t>(n_steps, per_pol);
+  // a workgroup's rows (its steps' NEW rows each + the WIN-row window) must fit one
+  // buffer descriptor: huge single series get more, shorter ranges
+  // (bytes from one sample of a series to its next: 8, or a DADA section's n_pol x 2 x NBIT / 8)
+  const int64_t sstep = a.din ? (int64_t)a.n_pol * (a.din_nbit / 4) : 8;
+  const int64_t fit_steps = (kRsrcMaxBytes / (sstep * N) - SH::WIN) / SH::NEW;
+  if (fit_steps <= 0) return hipErrorInvalidValue;
+  wgs = std::max(wgs, (n_steps + fit_steps - 1) / fit_steps);
+  *g = StreamGrid{n_steps, fit_steps, wgs, env_wpc};
+  return hipSuccess;
 }
 
 }  // namespace pfb

@@ -760,24 +760,13 @@ static hipError_t launch_stream(const AnalysisArgs& a, hipStream_t s) {
   if (a.pre && (a.pad < 0 || a.pad > (int64_t)SH::WIN * N)) return hipErrorInvalidValue;
   hipError_t e = set_lds(kern, SH::lds_bytes);
   if (e != hipSuccess) return e;
-  const int64_t q_lo = a.row0 / NU;
-  const int64_t n_steps = ((a.K + NU - 1) / NU - q_lo + SH::QS - 1) / SH::QS;
-  // LDS-limited resident workgroups per CU, each a contiguous range of steps
-  // two persistent workgroups per CU (one below the LDS-resident count of 3): longer step
-  // ranges amortise each workgroup's start-up window load; measured 4 % faster than 3
-  // (PFB_ANA_WG_PER_CU overrides, A/B knob)
-  int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / SH::lds_bytes));
-  static const int env_wpc = knob("PFB_ANA_WG_PER_CU") ? std::atoi(knob("PFB_ANA_WG_PER_CU")) : 0;
-  if (env_wpc > 0) per_cu = env_wpc;
-  const int64_t per_pol = std::max<int64_t>(1, (per_cu * cu_count()) / a.n_pol);
-  int64_t wgs = std::min<int64_t>(n_steps, per_pol);
-  // a workgroup's rows (its steps' NEW rows each + the WIN-row window) must fit one
-  // buffer descriptor: huge single series get more, shorter ranges
-  // (bytes from one sample of a series to its next: 8, or a DADA section's n_pol x 2 x NBIT / 8)
-  const int64_t sstep = a.din ? (int64_t)a.n_pol * (a.din_nbit / 4) : 8;
-  const int64_t fit_steps = (kRsrcMaxBytes / (sstep * N) - SH::WIN) / SH::NEW;
-  if (fit_steps <= 0) return hipErrorInvalidValue;
-  wgs = std::max(wgs, (n_steps + fit_steps - 1) / fit_steps);
+  // (the resident workgroup count and the descriptor fit: stream_grid, pfb_ana_stream.hpp)
+  StreamGrid sg;
+  e = stream_grid<SH, NU>(a, &sg);
+  if (e != hipSuccess) return e;
+  const int64_t n_steps = sg.n_steps, fit_steps = sg.fit_steps;
+  [[maybe_unused]] const int env_wpc = sg.env_wpc;
+  int64_t wgs = sg.wgs;
   // (PFB_ANA_STEPS=S: S steps per workgroup, ceil(n_steps / S) workgroups instead of the
   // resident count; PFB_ANA_LINEAR=1: linear workgroup order — experiments A/B)
   AnalysisArgs b = a;
@@ -860,6 +849,7 @@ static hipError_t launch_fused_v(const AnalysisArgs& a, hipStream_t s) {
 
 hipError_t launch_lowcbf_stream(const AnalysisArgs& a, hipStream_t s) {
   if (a.N != 256 || a.M != 192 || a.P != 12 || a.nu != 4) return hipErrorInvalidValue;
+  if (a.dout) return launch_stream_dadaout(a, true, s);
   return launch_stream<256, 12, 4, 3, true>(a, s);
 }
 
@@ -898,6 +888,11 @@ bool analysis_reads_dada(const AnalysisArgs& a, int nbit) {
   return fir_lds_shape(a, (int)((int64_t)a.M * a.nu / a.N));
 }
 
+bool analysis_writes_dada(const AnalysisArgs& a, int nbit) {
+  if (nbit != 8 && nbit != 16 && nbit != 32) return false;
+  return stream_shape(a) && knob("PFB_ANALYSIS_NO_STREAM") == nullptr;
+}
+
 bool analysis_takes_offset(const AnalysisArgs& a) {
   return stream_shape(a) && knob("PFB_ANALYSIS_NO_STREAM") == nullptr;
 }
@@ -920,8 +915,11 @@ hipError_t launch_analysis(const AnalysisArgs& a, hipStream_t s) {
     if (!stream_ok && !generic_ok) return hipErrorInvalidValue;
   }
   if (a.din && (!analysis_reads_dada(a, a.din_nbit) || a.z)) return hipErrorInvalidValue;
+  // (a DADA product: the streaming kernel's plain product only)
+  if (a.dout && (!analysis_writes_dada(a, a.dout_nbit) || a.z || a.out_rs != 0)) return hipErrorInvalidValue;
   static const bool no_stream = knob("PFB_ANALYSIS_NO_STREAM") != nullptr;
   if (fused && stream_shape(a) && !no_stream) {
+    if (a.dout) return launch_stream_dadaout(a, false, s);
     static const int mask = knob("PFB_ANA_MASK") ? std::atoi(knob("PFB_ANA_MASK")) : 0;
     AnalysisArgs b = a;
     b.timing_mask = mask;

@@ -239,6 +239,8 @@ struct pfb_analysis_plan {
   DevBuf carry_next;  // device streams: the streaming kernel writes the next carry here, then swap
   int64_t buffered = 0;
   int last_dada = PFB_DADA_INPUT_NONE;  // pfb_analysis_last_dada_input
+  int last_dada_out = PFB_DADA_OUTPUT_NONE;  // pfb_analysis_last_dada_output
+  DevBuf dada_stage;  // STAGED DADA output: the cf32 product before its scaled pack launch
   // round trip (pfb_roundtrip_execute): the analysis runs on this stream, ahead of the
   // synthesis on the caller's stream; one event per chunk orders them
   hipStream_t aux = nullptr;
@@ -276,16 +278,34 @@ struct AnaDada {
   int nbit;
 };
 
+// A DADA data section (TFP, NDIM 2, NBIT 8 / 16 / 32, aligned to a complex sample) the analysis
+// kernel writes instead of `out`, each component to_sample(scale * x)
+// (pfb_analysis_execute_to_dada, FUSED)
+struct AnaOut {
+  void* base;
+  int nbit;
+  float scale;
+};
+
 // dd: the launch reads the section instead of `in` (analysis_dada_fusable plans only)
+// od: the launch writes the section instead of `out` (analysis_dada_out_fusable plans only;
+// `out` and out_ps are ignored)
 static pfb_status analysis_run(pfb_analysis_plan* p, const float2* in, int64_t in_ps, int64_t n_dat,
                                float2* out, int64_t out_ps, int64_t row0, int64_t K_end,
                                int64_t K_total, hipStream_t s, float2* z = nullptr,
                                int64_t z_ps = 0, int64_t z_row0 = 0, int64_t pad = 0,
                                const OutLayout* lay = nullptr, int zblk = 0, const float2* pre = nullptr,
-                               int z_stage = 0, const CarryOut* co = nullptr, const AnaDada* dd = nullptr) {
+                               int z_stage = 0, const CarryOut* co = nullptr, const AnaDada* dd = nullptr,
+                               const AnaOut* od = nullptr) {
   if (K_end <= row0) return PFB_OK;
   if (dd) p->last_dada = PFB_DADA_INPUT_FUSED;
+  if (od) {
+    if (z || lay || row0 != 0) return fail(PFB_ERR_UNSUPPORTED, "DADA output: the plain product only");
+    out = nullptr;
+    out_ps = 0;
+  }
   const double in_b = dd ? 2.0 * (dd->nbit / 8) : 8.0;  // bytes per input sample
+  const double out_b = od ? 2.0 * (od->nbit / 8) : 8.0;  // bytes per output sample
   if (p->variant == pfb::kLowCbf) {
     pfb::LowCbfArgs l{};
     l.in = in;
@@ -298,6 +318,11 @@ static pfb_status analysis_run(pfb_analysis_plan* p, const float2* in, int64_t i
       l.din = dd->base;
       l.din_nbit = dd->nbit;
     }
+    if (od) {
+      l.dout = od->base;
+      l.dout_nbit = od->nbit;
+      l.dout_scale = od->scale;
+    }
     l.out = out;
     l.out_pol_stride = out_ps;
     l.K = K_end;
@@ -305,7 +330,7 @@ static pfb_status analysis_run(pfb_analysis_plan* p, const float2* in, int64_t i
     l.taps = p->taps.as<float>();
     l.tw = p->twN.as<float2>();
     l.scale = 4096.0f;  // 2^9 * 2048 * 256 / 2^9 / 128
-    ProfScope ps(0, (double)p->n_pol * (in_b * n_dat + 8.0 * K_end * p->C), s);
+    ProfScope ps(0, (double)p->n_pol * (in_b * n_dat + out_b * K_end * p->C), s);
     HIPCHK(pfb::launch_lowcbf(l, s));
     return PFB_OK;
   }
@@ -322,6 +347,11 @@ static pfb_status analysis_run(pfb_analysis_plan* p, const float2* in, int64_t i
     a.din = dd->base;
     a.din_nbit = dd->nbit;
   }
+  if (od) {
+    a.dout = od->base;
+    a.dout_nbit = od->nbit;
+    a.dout_scale = od->scale;
+  }
   a.scratch = nullptr;
   if (!p->fused && !z) {
     HIPCHK(p->scratch.ensure((size_t)p->n_pol * (K_end - row0) * p->N * sizeof(float2)));
@@ -334,7 +364,7 @@ static pfb_status analysis_run(pfb_analysis_plan* p, const float2* in, int64_t i
                                  : (K_end - row0) * p->M + (K_end == K_total ? n_dat - K_total * p->M : 0);
   // (with z: the stage-1 rows are a synthesis intermediate, not algorithmic bytes —
   // the synthesis' algorithmic read of its input is counted by the block kernel)
-  const double bytes = (double)p->n_pol * (in_b * in_samples + 8.0 * (K_end - row0) * p->N);
+  const double bytes = (double)p->n_pol * (in_b * in_samples + out_b * (K_end - row0) * p->N);
   // generic path = FIR + row FFT launches (z_stage 1 / 2: one of them, timed as its own
   // class; their bytes: the FIR reads the input and writes the stage-1 rows, the row FFT
   // reads them and writes the channelised product)
@@ -423,6 +453,25 @@ static bool analysis_dada_fusable(const pfb_analysis_plan* p, const void* base, 
     a.variant = pfb::kBunton;
   }
   return pfb::analysis_reads_dada(a, nbit);
+}
+
+// FUSED output (pfb_api.h): the plan's kernel stores such a section itself
+static bool analysis_dada_out_fusable(const pfb_analysis_plan* p, const void* base, int nbit) {
+  if (nbit != 8 && nbit != 16 && nbit != 32) return false;
+  if (reinterpret_cast<uintptr_t>(base) % (size_t)(nbit / 4) != 0) return false;
+  pfb::AnalysisArgs a{};
+  a.variant = p->variant;
+  a.N = p->N;
+  a.M = p->M;
+  a.P = p->P;
+  a.nu = p->nu;
+  a.n_pol = p->n_pol;
+  if (p->variant == pfb::kLowCbf) {
+    // (the streaming kernel's LCBF instantiation: analysis_dada_fusable's note)
+    if (pfb::knob("PFB_LOWCBF_STREAM") && std::atoi(pfb::knob("PFB_LOWCBF_STREAM")) == 0) return false;
+    a.variant = pfb::kBunton;
+  }
+  return pfb::analysis_writes_dada(a, nbit);
 }
 
 static bool analysis_fused_carry_ok(const pfb_analysis_plan* p) {
@@ -559,7 +608,7 @@ static void analysis_host_tables(const pfb_analysis_desc* d, const pfb_analysis_
 
 static void analysis_release(pfb_analysis_plan* p) {
   for (DevBuf* b : {&p->taps, &p->twN, &p->zrev, &p->gtab, &p->scratch, &p->carry, &p->carry_next, &p->work, &p->stage_in,
-                    &p->stage_out})
+                    &p->stage_out, &p->dada_stage})
     b->release();
 }
 
@@ -625,7 +674,14 @@ int64_t pfb_analysis_output_length(const pfb_analysis_plan* p, int64_t n_dat) {
 struct AnaSection {
   const void* base;
   int nbit, ndim, order;
+  // unpack it even where the kernel could read it in place (a _dada_to_dada call whose NBIT
+  // pair the DADA-store kernels do not read in place: pfb::dadaout_reads_dada)
+  bool force_staged = false;
 };
+
+static bool ana_section_fusable(const pfb_analysis_plan* p, const AnaSection& sec) {
+  return !sec.force_staged && analysis_dada_fusable(p, sec.base, sec.nbit, sec.ndim, sec.order);
+}
 
 static pfb_status ana_section_check(const pfb_analysis_plan* p, const AnaSection& sec, int64_t n) {
   if (!p) return fail(PFB_ERR_INVALID_ARG, "null plan");
@@ -649,10 +705,12 @@ static pfb_status ana_section_unpack(const pfb_analysis_plan* p, const AnaSectio
                          s);
 }
 
-// pfb_analysis_execute; sec: the series are a DADA section (device memory) instead of `in`
+// pfb_analysis_execute; sec: the series are a DADA section (device memory) instead of `in`;
+// od: the product goes out as a DADA section (device memory, FUSED) instead of `out`, which
+// then only has to pass the checks
 static pfb_status analysis_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps, const AnaSection* sec,
                                 int64_t n_dat, pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
-                                int32_t mem, void* stream) {
+                                int32_t mem, void* stream, const AnaOut* od = nullptr) {
   if (sec) in = static_cast<const pfb_cf32*>(sec->base);
   if (!p || (!in && n_dat > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
   if (n_dat < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_dat");
@@ -665,9 +723,7 @@ static pfb_status analysis_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_
   if (K == 0) {
     pad_once.accept();
     // (no launch: the path the section's rows would have taken)
-    if (sec)
-      p->last_dada = analysis_dada_fusable(p, sec->base, sec->nbit, sec->ndim, sec->order) ? PFB_DADA_INPUT_FUSED
-                                                                                         : PFB_DADA_INPUT_STAGED;
+    if (sec) p->last_dada = ana_section_fusable(p, *sec) ? PFB_DADA_INPUT_FUSED : PFB_DADA_INPUT_STAGED;
     return PFB_OK;
   }
   if (!out) return fail(PFB_ERR_INVALID_ARG, "null output");
@@ -677,19 +733,21 @@ static pfb_status analysis_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_
     return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
   pad_once.accept();
   if (sec) {
-    if (analysis_dada_fusable(p, sec->base, sec->nbit, sec->ndim, sec->order)) {
+    if (ana_section_fusable(p, *sec)) {
       const AnaDada dd{sec->base, sec->nbit};
       return analysis_run(p, nullptr, 0, n_dat, (float2*)out, out_ps, 0, K, K, s, nullptr, 0, 0, 0, nullptr, 0,
-                          nullptr, 0, nullptr, &dd);
+                          nullptr, 0, nullptr, &dd, od);
     }
     HIPCHK(p->stage_in.ensure((size_t)p->n_pol * n_dat * sizeof(float2)));
     p->last_dada = PFB_DADA_INPUT_STAGED;
     const pfb_status st = ana_section_unpack(p, *sec, 0, n_dat, p->stage_in.as<float2>(), n_dat, s);
     if (st != PFB_OK) return st;
-    return analysis_run(p, p->stage_in.as<float2>(), n_dat, n_dat, (float2*)out, out_ps, 0, K, K, s);
+    return analysis_run(p, p->stage_in.as<float2>(), n_dat, n_dat, (float2*)out, out_ps, 0, K, K, s, nullptr, 0, 0, 0,
+                        nullptr, 0, nullptr, 0, nullptr, nullptr, od);
   }
   if (mem == PFB_MEM_DEVICE) {
-    return analysis_run(p, (const float2*)in, in_ps, n_dat, (float2*)out, out_ps, 0, K, K, s);
+    return analysis_run(p, (const float2*)in, in_ps, n_dat, (float2*)out, out_ps, 0, K, K, s, nullptr, 0, 0, 0,
+                        nullptr, 0, nullptr, 0, nullptr, nullptr, od);
   }
   // host staging (synchronous)
   HIPCHK(p->stage_in.ensure((size_t)p->n_pol * n_dat * sizeof(float2)));
@@ -705,10 +763,16 @@ static pfb_status analysis_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_
   return PFB_OK;
 }
 
+// a cf32-output call that went through: pfb_analysis_last_dada_output reports NONE again
+static pfb_status cf32_output(pfb_analysis_plan* p, pfb_status st) {
+  if (p && st == PFB_OK) p->last_dada_out = PFB_DADA_OUTPUT_NONE;
+  return st;
+}
+
 pfb_status pfb_analysis_execute(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps,
                                 int64_t n_dat, pfb_cf32* out, int64_t out_ps, int64_t cap,
                                 int64_t* n_out, int32_t mem, void* stream) {
-  return analysis_exec(p, in, in_ps, nullptr, n_dat, out, out_ps, cap, n_out, mem, stream);
+  return cf32_output(p, analysis_exec(p, in, in_ps, nullptr, n_dat, out, out_ps, cap, n_out, mem, stream));
 }
 
 pfb_status pfb_analysis_execute_dada(pfb_analysis_plan* p, const void* in, int32_t nbit, int32_t ndim,
@@ -717,14 +781,15 @@ pfb_status pfb_analysis_execute_dada(pfb_analysis_plan* p, const void* in, int32
   const AnaSection sec{in, nbit, ndim, order};
   const pfb_status st = ana_section_check(p, sec, n_dat);
   if (st != PFB_OK) return st;
-  return analysis_exec(p, nullptr, 0, &sec, n_dat, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream);
+  return cf32_output(p, analysis_exec(p, nullptr, 0, &sec, n_dat, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream));
 }
 
 int32_t pfb_analysis_last_dada_input(const pfb_analysis_plan* p) { return p ? p->last_dada : -1; }
 
 static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps, int64_t n_in,
                                   pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out, int32_t mem,
-                                  void* stream, const OutLayout* lay, const AnaSection* sec = nullptr);
+                                  void* stream, const OutLayout* lay, const AnaSection* sec = nullptr,
+                                  const AnaOut* od = nullptr);
 
 pfb_status pfb_filterbank_execute_dada(pfb_analysis_plan* p, const void* in, int32_t nbit, int32_t ndim,
                                        int32_t order, int64_t n_in, pfb_cf32* out, int64_t out_ps, int64_t cap,
@@ -732,13 +797,14 @@ pfb_status pfb_filterbank_execute_dada(pfb_analysis_plan* p, const void* in, int
   const AnaSection sec{in, nbit, ndim, order};
   const pfb_status st = ana_section_check(p, sec, n_in);
   if (st != PFB_OK) return st;
-  return filterbank_exec(p, nullptr, 0, n_in, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream, nullptr, &sec);
+  return cf32_output(
+      p, filterbank_exec(p, nullptr, 0, n_in, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream, nullptr, &sec));
 }
 
 pfb_status pfb_filterbank_execute(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps,
                                   int64_t n_in, pfb_cf32* out, int64_t out_ps, int64_t cap,
                                   int64_t* n_out, int32_t mem, void* stream) {
-  return filterbank_exec(p, in, in_ps, n_in, out, out_ps, cap, n_out, mem, stream, nullptr);
+  return cf32_output(p, filterbank_exec(p, in, in_ps, n_in, out, out_ps, cap, n_out, mem, stream, nullptr));
 }
 
 int64_t pfb_filterbank_output_rows(const pfb_analysis_plan* p, int64_t n_in) {
@@ -786,17 +852,113 @@ pfb_status pfb_filterbank_execute_strided(pfb_analysis_plan* p, const pfb_cf32* 
                   (long long)last, (long long)cap);
   }
   const OutLayout lay{row_stride, chan_stride, sel_split, sel_shift, sel_n, std::max<int64_t>(Kt, 0)};
-  return filterbank_exec(p, in, in_ps, n_in, out, out_ps, std::max<int64_t>(Kt, 0), n_out, PFB_MEM_DEVICE,
-                         stream, &lay);
+  return cf32_output(p, filterbank_exec(p, in, in_ps, n_in, out, out_ps, std::max<int64_t>(Kt, 0), n_out,
+                                        PFB_MEM_DEVICE, stream, &lay));
 }
+
+// The to-DADA calls (pfb_api.h): every check here, before the callee launches or changes the
+// stream state; then FUSED — the kernel stores the section (od) — or STAGED — the cf32 path
+// into the plan's buffer and the scaled pack launch.
+static pfb_status analysis_to_dada(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps, const AnaSection* sec_in,
+                                   int64_t n, void* out, int32_t nbit, float scale, int64_t cap_bytes,
+                                   int64_t* n_out, void* stream, bool stream_call) {
+  if (!p) return fail(PFB_ERR_INVALID_ARG, "null plan");
+  if (nbit != 8 && nbit != 16 && nbit != 32 && nbit != 64)
+    return fail(PFB_ERR_INVALID_ARG, "output NBIT must be 8, 16, 32 or 64");
+  if (!std::isfinite(scale)) return fail(PFB_ERR_INVALID_ARG, "output scale is not finite");
+  if (reinterpret_cast<uintptr_t>(out) % (size_t)(nbit / 8) != 0)
+    return fail(PFB_ERR_INVALID_ARG, "output section not aligned to its NBIT");
+  // the input-side conditions of the corresponding cf32-output call
+  if (sec_in) {
+    const pfb_status st = ana_section_check(p, *sec_in, n);
+    if (st != PFB_OK) return st;
+  }
+  if (!(sec_in ? sec_in->base : (const void*)in) && n > 0) return fail(PFB_ERR_INVALID_ARG, "null argument");
+  if (n < 0) return fail(PFB_ERR_INVALID_ARG, "negative sample count");
+  if (!sec_in && in_ps < n) return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
+  // K: the rows the callee computes (the padded variant's shift spans all of them); rows: the
+  // rows it returns (a stream call trims to a multiple of nu, FilterBank.m:93-104)
+  const int64_t K = analysis_K(p, stream_call ? p->buffered + n : n);
+  const int64_t rows = stream_call ? K - (K % p->nu) : K;
+  if (n_out) *n_out = rows;
+  if (rows > 0) {
+    if (!out) return fail(PFB_ERR_INVALID_ARG, "null output");
+    const int64_t need = rows * p->C * p->n_pol * 2 * (nbit / 8);
+    if (cap_bytes < need)
+      return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld bytes", (long long)cap_bytes,
+                  (long long)need);
+  }
+  HIPCHK(hipSetDevice(p->device));
+  const bool fused = analysis_dada_out_fusable(p, out, nbit);
+  AnaSection sec{};
+  if (sec_in) {
+    sec = *sec_in;
+    // (the DADA-store kernels read cf32, a section of the output's NBIT, or an integer
+    // section when they write NBIT 32)
+    if (fused && !pfb::dadaout_reads_dada(sec.nbit, nbit)) sec.force_staged = true;
+  }
+  const AnaSection* sp = sec_in ? &sec : nullptr;
+  pfb_status st;
+  if (fused) {
+    // (`out` stands in for the cf32 buffer in the callee's null, capacity and stride checks:
+    // rows packed rows of capacity; the launch writes through od only)
+    const AnaOut od{out, nbit, scale};
+    pfb_cf32* o = static_cast<pfb_cf32*>(out);
+    st = stream_call ? filterbank_exec(p, in, in_ps, n, o, rows * p->C, rows, n_out, PFB_MEM_DEVICE, stream, nullptr,
+                                       sp, &od)
+                     : analysis_exec(p, in, in_ps, sp, n, o, rows * p->C, rows, n_out, PFB_MEM_DEVICE, stream, &od);
+  } else {
+    // all K computed rows have room (a padded stream call then runs straight into the buffer)
+    HIPCHK(p->dada_stage.ensure((size_t)p->n_pol * std::max<int64_t>(K, 1) * p->C * sizeof(float2)));
+    pfb_cf32* o = p->dada_stage.as<pfb_cf32>();
+    st = stream_call
+             ? filterbank_exec(p, in, in_ps, n, o, K * p->C, K, n_out, PFB_MEM_DEVICE, stream, nullptr, sp)
+             : analysis_exec(p, in, in_ps, sp, n, o, K * p->C, K, n_out, PFB_MEM_DEVICE, stream);
+    if (st == PFB_OK)
+      HIPCHK(pfb::launch_dada_pack_scaled(p->dada_stage.as<float2>(), K * p->C, rows, p->C, p->n_pol, out, nbit,
+                                          scale, (hipStream_t)stream));
+  }
+  if (st == PFB_OK) p->last_dada_out = fused ? PFB_DADA_OUTPUT_FUSED : PFB_DADA_OUTPUT_STAGED;
+  return st;
+}
+
+pfb_status pfb_analysis_execute_to_dada(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps, int64_t n_dat,
+                                        void* out, int32_t out_nbit, float out_scale, int64_t cap_bytes,
+                                        int64_t* n_out, void* stream) {
+  return analysis_to_dada(p, in, in_ps, nullptr, n_dat, out, out_nbit, out_scale, cap_bytes, n_out, stream, false);
+}
+
+pfb_status pfb_filterbank_execute_to_dada(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps, int64_t n_in,
+                                          void* out, int32_t out_nbit, float out_scale, int64_t cap_bytes,
+                                          int64_t* n_out, void* stream) {
+  return analysis_to_dada(p, in, in_ps, nullptr, n_in, out, out_nbit, out_scale, cap_bytes, n_out, stream, true);
+}
+
+pfb_status pfb_analysis_execute_dada_to_dada(pfb_analysis_plan* p, const void* in, int32_t nbit, int32_t ndim,
+                                             int32_t order, int64_t n_dat, void* out, int32_t out_nbit,
+                                             float out_scale, int64_t cap_bytes, int64_t* n_out, void* stream) {
+  const AnaSection sec{in, nbit, ndim, order};
+  return analysis_to_dada(p, nullptr, 0, &sec, n_dat, out, out_nbit, out_scale, cap_bytes, n_out, stream, false);
+}
+
+pfb_status pfb_filterbank_execute_dada_to_dada(pfb_analysis_plan* p, const void* in, int32_t nbit, int32_t ndim,
+                                               int32_t order, int64_t n_in, void* out, int32_t out_nbit,
+                                               float out_scale, int64_t cap_bytes, int64_t* n_out, void* stream) {
+  const AnaSection sec{in, nbit, ndim, order};
+  return analysis_to_dada(p, nullptr, 0, &sec, n_in, out, out_nbit, out_scale, cap_bytes, n_out, stream, true);
+}
+
+int32_t pfb_analysis_last_dada_output(const pfb_analysis_plan* p) { return p ? p->last_dada_out : -1; }
 
 }  // extern "C"
 
 // sec: the new samples are a DADA section (device memory) instead of `in`.  The carry stays
 // packed cf32, so cf32 and DADA calls may alternate on one plan.
+// od: the rows go out as a DADA section (device memory, FUSED: a plan on the streaming kernel)
+// instead of `out`, which then only has to pass the checks.
 static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps, int64_t n_in,
                                   pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out, int32_t mem,
-                                  void* stream, const OutLayout* lay, const AnaSection* sec) {
+                                  void* stream, const OutLayout* lay, const AnaSection* sec, const AnaOut* od) {
   if (sec) {
     in = static_cast<const pfb_cf32*>(sec->base);
     in_ps = n_in;
@@ -807,7 +969,7 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
   hipStream_t s = (hipStream_t)stream;
   // FUSED: the kernel reads the section's new samples in place; STAGED: they are unpacked
   // behind the carry in the concatenation buffer and the cf32 path runs
-  const bool fus = sec && analysis_dada_fusable(p, sec->base, sec->nbit, sec->ndim, sec->order);
+  const bool fus = sec && ana_section_fusable(p, *sec);
   const AnaDada dd_{sec ? sec->base : nullptr, sec ? sec->nbit : 0};
   const AnaDada* dd = fus ? &dd_ : nullptr;
   const int last_dada = !sec ? PFB_DADA_INPUT_NONE : PFB_DADA_INPUT_STAGED;  // (a fused launch sets FUSED)
@@ -867,7 +1029,7 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
       // (the LowCBF instantiation has no carry copy: unpacked by a launch behind it)
       pfb_status st = analysis_run(p, (const float2*)in, in_ps, n_in, (float2*)out, out_ps, 0, Kt, K, s,
                                    nullptr, 0, 0, B, lay, 0, p->carry.as<float2>(), 0,
-                                   nb > 0 && !lcbf_dd ? &co : nullptr, dd);
+                                   nb > 0 && !lcbf_dd ? &co : nullptr, dd, od);
       if (st != PFB_OK) return st;
       if (lcbf_dd) {
         st = ana_section_unpack(p, *sec, input_idat - B, nb, co.dst, nb, s);
@@ -891,7 +1053,7 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
     // take the streaming kernel above — goes straight to `out`: the launch stores the shifted
     // rows below Kt through the layout and drops rows [Kt, K), so there are no scratch rows
     // and no staging buffer)
-    if (!sec && mem == PFB_MEM_DEVICE && B > 0 && !p->lowcbf_pad && p->fused && analysis_fused_carry_ok(p) &&
+    if (!sec && !od && mem == PFB_MEM_DEVICE && B > 0 && !p->lowcbf_pad && p->fused && analysis_fused_carry_ok(p) &&
         input_idat >= B && Kt > 0) {
       p->last_dada = last_dada;
       if (n_out) *n_out = Kt;
@@ -985,7 +1147,7 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
       }
     }
     pfb_status st = analysis_run(p, w, wps, total, dst, dps, 0, Krun, K, s, nullptr, 0, 0, 0, lay, 0, nullptr, 0,
-                                 nullptr, dd);
+                                 nullptr, dd, od);
     if (st != PFB_OK) return st;
     if (dst != (float2*)out) {
       const hipMemcpyKind ko = mem == PFB_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;

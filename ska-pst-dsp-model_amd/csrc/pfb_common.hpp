@@ -56,6 +56,15 @@ constexpr int kAuxColMajor = PFB_AUX_COLMAJOR;
 #define PFB_AUX_LCBF PFB_AUX_CHAN
 #endif
 constexpr int kAuxLcbf = PFB_AUX_LCBF;
+// DADA sections stored by the streaming analysis (OutDada8 / 16 / 32): the default policy.  A
+// two-polarisation section is filled by two workgroups, every other complex sample each, at
+// different times; written nontemporal like the channelised rows the half-filled lines cost
+// 12 % (C2, NBIT 16) to 2 x (LowCBF) more time, against 0-7 % gained on one polarisation
+// (profiles/dada_output_ab.jsonl)
+#ifndef PFB_AUX_DADAOUT
+#define PFB_AUX_DADAOUT 0
+#endif
+constexpr int kAuxDadaOut = PFB_AUX_DADAOUT;
 // the same for the C3 (SKA-Mid, N > 256) kernels' streams, nontemporal (1) or default (0):
 // the FIR's stage-1 rows (PFB_NT_FIRZ), the row FFT's rows (RowStore, PFB_NT_ROW), the
 // synth_wave512 output (PFB_NT_W5).  Measured: the C3 round trip 0.960/0.967 -> 0.936/0.954

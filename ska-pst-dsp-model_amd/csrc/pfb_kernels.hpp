@@ -108,10 +108,31 @@ struct AnalysisArgs {
   // as ever; `in` and in_pol_stride are unused.
   const void* din = nullptr;
   int din_nbit = 0;
+  // The product goes out as a DADA data section instead of `out`
+  // (pfb_analysis_execute_to_dada; analysis_writes_dada): TFP order, NDIM 2, dout_nbit 8 / 16
+  // (integers) or 32 (float); element (row k, channel c, pol p) at byte
+  // ((k C + c) n_pol + p) dout_nbit / 4 of dout, C = N (216 for the LowCBF instantiation), its
+  // value to_sample(dout_scale * x) per component of the x the cf32 kernel stores.  dout is
+  // aligned to one complex sample; `out` and out_pol_stride are unused.  A DADA input (din)
+  // has the same NBIT, or dout_nbit is 32 (dadaout_reads_dada).
+  void* dout = nullptr;
+  int dout_nbit = 0;
+  float dout_scale = 1.f;
 };
 // the plan's kernel has a loader for such a section (the streaming kernel; the LDS-shared FIR
 // of the N > 256 path, launches without stage-1 rows)
 bool analysis_reads_dada(const AnalysisArgs& a, int nbit);
+// the plan's kernel has a DADA store (the streaming kernel)
+bool analysis_writes_dada(const AnalysisArgs& a, int nbit);
+// the streaming kernel with the DADA store (pfb_ana_stream_dadaout.hip); lcbf: the LowCBF
+// instantiation (launch_lowcbf_stream's shape)
+hipError_t launch_stream_dadaout(const AnalysisArgs& a, bool lcbf, hipStream_t s);
+// those kernels read a DADA section of in_nbit in place when they write out_nbit (the same
+// NBIT, or any integer NBIT into NBIT 32); other pairs come in unpacked, as cf32
+bool dadaout_reads_dada(int in_nbit, int out_nbit);
+// pfb_dada_pack with both components multiplied by `scale` in float32 first (pfb_layout.hip)
+hipError_t launch_dada_pack_scaled(const float2* in, int64_t in_pol_stride, int64_t n_dat, int C, int P,
+                                   void* out, int nbit, float scale, hipStream_t s);
 // SKA-Low CBF PST filterbank through the streaming analysis kernel (pfb_analysis.hip)
 hipError_t launch_lowcbf_stream(const AnalysisArgs& a, hipStream_t s);
 // analysis kernels that can also emit the synthesis stage-1 rows (see AnalysisArgs::z)
@@ -276,6 +297,10 @@ struct LowCbfArgs {
   // the input is a DADA section read in place (AnalysisArgs::din; streaming path only)
   const void* din = nullptr;
   int din_nbit = 0;
+  // the product goes out as a DADA section (AnalysisArgs::dout; streaming path only)
+  void* dout = nullptr;
+  int dout_nbit = 0;
+  float dout_scale = 1.f;
 };
 hipError_t launch_lowcbf(const LowCbfArgs& a, hipStream_t s);
 

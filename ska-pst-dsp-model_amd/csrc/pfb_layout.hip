@@ -28,6 +28,7 @@
 
 #include "pfb_api.h"
 #include "pfb_kernels.hpp"
+#include "pfb_sample.hpp"
 
 pfb_status pfb_set_error(pfb_status s, const char* msg);  // pfb_api.hip
 
@@ -50,21 +51,7 @@ constexpr int TPB = 256;
 
 unsigned blocks_for(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
-// Matlab cast(single -> intN): round half away from zero, saturate, NaN -> 0
-template <class T>
-__device__ __forceinline__ T to_sample(float v) {
-  if constexpr (std::is_same<T, float>::value) {
-    return v;
-  } else if constexpr (std::is_same<T, double>::value) {
-    return (double)v;
-  } else {
-    constexpr float lo = (float)std::numeric_limits<T>::min();
-    constexpr float hi = (float)std::numeric_limits<T>::max();
-    if (v != v) return (T)0;
-    const float r = roundf(v);
-    return (T)fminf(fmaxf(r, lo), hi);
-  }
-}
+using pfb::to_sample;  // pfb_sample.hpp
 
 // ---------------------------------------------------------------- DADA unpack / pack
 // One thread per (t, c): reads the P (x NDIM) adjacent file samples of its (t, c) and
@@ -97,6 +84,22 @@ __global__ void __launch_bounds__(TPB) dada_pack_kernel(const float2* __restrict
     const int64_t e = i * P + p;  // (t * C + c) * P + p
     out[2 * e] = to_sample<T>(v.x);
     out[2 * e + 1] = to_sample<T>(v.y);
+  }
+}
+
+// dada_pack_kernel with both components multiplied by `scale` in float32 first: the pack
+// launch of the STAGED analysis-to-DADA calls (pfb_analysis_execute_to_dada)
+template <class T>
+__global__ void __launch_bounds__(TPB) dada_pack_scaled_kernel(const float2* __restrict__ in, int64_t ips,
+                                                               int64_t n_dat, int C, int P, float scale,
+                                                               T* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n_dat * C) return;
+  for (int p = 0; p < P; ++p) {
+    const float2 v = in[p * ips + i];
+    const int64_t e = i * P + p;  // (t * C + c) * P + p
+    out[2 * e] = to_sample<T>(scale * v.x);
+    out[2 * e + 1] = to_sample<T>(scale * v.y);
   }
 }
 
@@ -182,6 +185,21 @@ hipError_t pfb::launch_dada_unpack_rows(const pfb::DadaIn& d, int64_t n_rows, in
   const int64_t t0 = d.lowcbf ? d.t0 : 0;
   return d.nbit == 8 ? launch_unpack<int8_t>(in, 2, d.lowcbf != 0, n_rows, C, P, out, ops, s, t0)
                      : launch_unpack<int16_t>(in, 2, d.lowcbf != 0, n_rows, C, P, out, ops, s, t0);
+}
+
+hipError_t pfb::launch_dada_pack_scaled(const float2* in, int64_t ips, int64_t n_dat, int C, int P, void* out,
+                                        int nbit, float scale, hipStream_t s) {
+  if (n_dat <= 0) return hipSuccess;
+  if (!in || !out || C <= 0 || P <= 0 || ips < n_dat * C) return hipErrorInvalidValue;
+  const unsigned g = blocks_for(n_dat * C);
+  switch (nbit) {
+    case 8: hipLaunchKernelGGL(dada_pack_scaled_kernel<int8_t>, g, TPB, 0, s, in, ips, n_dat, C, P, scale, (int8_t*)out); break;
+    case 16: hipLaunchKernelGGL(dada_pack_scaled_kernel<int16_t>, g, TPB, 0, s, in, ips, n_dat, C, P, scale, (int16_t*)out); break;
+    case 32: hipLaunchKernelGGL(dada_pack_scaled_kernel<float>, g, TPB, 0, s, in, ips, n_dat, C, P, scale, (float*)out); break;
+    case 64: hipLaunchKernelGGL(dada_pack_scaled_kernel<double>, g, TPB, 0, s, in, ips, n_dat, C, P, scale, (double*)out); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
 }
 
 namespace {

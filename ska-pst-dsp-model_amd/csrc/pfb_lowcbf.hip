@@ -152,10 +152,13 @@ hipError_t launch_lowcbf(const LowCbfArgs& a, hipStream_t s) {
     b.pre_pol_stride = a.pad;
     b.din = a.din;
     b.din_nbit = a.din_nbit;
+    b.dout = a.dout;
+    b.dout_nbit = a.dout_nbit;
+    b.dout_scale = a.dout_scale;
     return launch_lowcbf_stream(b, s);
   }
-  // (the one-shot kernel reads packed cf32 without a carry)
-  if (a.din || a.pre) return hipErrorInvalidValue;
+  // (the one-shot kernel reads packed cf32 without a carry and writes packed cf32)
+  if (a.din || a.pre || a.dout) return hipErrorInvalidValue;
   static_assert(NT == LN, "one thread per polyphase arm");
   const size_t bytes = ((size_t)LROWS * lds_row(LN) + tw_slots(LN)) * sizeof(float2);
   hipError_t e = set_lds(lowcbf_kernel, bytes);

@@ -44,6 +44,9 @@ PFB_DADA_LOWCBF = 1
 PFB_DADA_INPUT_NONE = 0
 PFB_DADA_INPUT_FUSED = 1
 PFB_DADA_INPUT_STAGED = 2
+PFB_DADA_OUTPUT_NONE = 0
+PFB_DADA_OUTPUT_FUSED = 1
+PFB_DADA_OUTPUT_STAGED = 2
 PFB_STRIDED_INPUT_NONE = 0
 PFB_STRIDED_INPUT_IN_PLACE = 1
 PFB_STRIDED_INPUT_STAGED = 2
@@ -132,6 +135,17 @@ SYMBOLS = [
     ("pfb_filterbank_execute_dada", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64,
                                               c_void_p, c_int64, c_int64, POINTER(c_int64), c_void_p]),
     ("pfb_analysis_last_dada_input", c_int32, [c_void_p]),
+    ("pfb_analysis_execute_to_dada", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32,
+                                               c_float, c_int64, POINTER(c_int64), c_void_p]),
+    ("pfb_filterbank_execute_to_dada", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32,
+                                                 c_float, c_int64, POINTER(c_int64), c_void_p]),
+    ("pfb_analysis_execute_dada_to_dada", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64,
+                                                    c_void_p, c_int32, c_float, c_int64, POINTER(c_int64),
+                                                    c_void_p]),
+    ("pfb_filterbank_execute_dada_to_dada", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64,
+                                                      c_void_p, c_int32, c_float, c_int64, POINTER(c_int64),
+                                                      c_void_p]),
+    ("pfb_analysis_last_dada_output", c_int32, [c_void_p]),
     ("pfb_synthesis_execute_strided", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
                                                 c_int64, c_int64, c_void_p, c_int64, c_int64,
                                                 POINTER(c_int64), c_void_p]),

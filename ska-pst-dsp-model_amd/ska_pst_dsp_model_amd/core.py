@@ -257,6 +257,71 @@ class AnalysisPlan:
         m = int(self._lib.pfb_analysis_last_dada_input(self._h))
         return {_lib.PFB_DADA_INPUT_FUSED: "fused", _lib.PFB_DADA_INPUT_STAGED: "staged"}.get(m, "none")
 
+    def _alloc_section(self, like, rows: int, out_nbit: int):
+        """-> (device tensor (rows, out_chan, n_pol, 2) of the DADA sample type, its bytes)."""
+        t = _torch()
+        types = {8: t.int8, 16: t.int16, 32: t.float32, 64: t.float64}
+        if int(out_nbit) not in types:
+            # (the C ABI rejects the format; a byte tensor stands in)
+            return t.empty((0, self.out_chan, self.n_pol, 2), dtype=t.int8, device=like.device), 0
+        sec = t.empty((max(rows, 0), self.out_chan, self.n_pol, 2), dtype=types[int(out_nbit)],
+                      device=like.device)
+        return sec, sec.numel() * sec.element_size()
+
+    def execute_to_dada(self, x, out_nbit: int, scale: float = 1.0, stateful: bool = False):
+        """The analysis of device series ``x`` written as a DADA data section: bit for bit
+        ``layout.dada_pack(float32(scale) * execute(x), out_nbit)`` — TFP order, NDIM 2 —
+        without the complex float32 product crossing HBM where the analysis kernel can store
+        the samples itself (pfb_analysis_execute_to_dada / pfb_filterbank_execute_to_dada;
+        ``last_dada_output()`` tells).  Returns a device tensor of shape
+        (K, n_chan, n_pol, 2), int8 / int16 / float32 / float64."""
+        if not is_device_array(x):
+            raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "execute_to_dada: expects a device tensor")
+        x, _ = self._prep_in(x)
+        if x.shape[0] != self.n_pol:
+            raise ValueError(f"plan built for n_pol={self.n_pol}, got {x.shape[0]}")
+        n_dat = x.shape[1]
+        rows = self.stream_rows(n_dat) if stateful else self.output_length(n_dat)
+        sec, nbytes = self._alloc_section(x, rows, out_nbit)
+        n_out = c_int64(0)
+        fn = self._lib.pfb_filterbank_execute_to_dada if stateful else self._lib.pfb_analysis_execute_to_dada
+        _lib.check(fn(self._h, c_void_p(x.data_ptr()), n_dat, n_dat, c_void_p(sec.data_ptr()), int(out_nbit),
+                      float(scale), nbytes, byref(n_out), _stream_of(x, self)))
+        return sec[:n_out.value]
+
+    def execute_dada_to_dada(self, raw, nbit: int, out_nbit: int, scale: float = 1.0, ndim: int = 2,
+                             lowcbf: bool = False, stateful: bool = False):
+        """``execute_dada`` written as a DADA data section like ``execute_to_dada``: file
+        bytes in, file bytes out (pfb_analysis_execute_dada_to_dada /
+        pfb_filterbank_execute_dada_to_dada); ``last_dada_input()`` and
+        ``last_dada_output()`` tell which sides the kernel read and wrote in place."""
+        if not is_device_array(raw):
+            raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "execute_dada_to_dada: expects a device tensor")
+        raw = raw.contiguous()
+        if int(nbit) not in (8, 16, 32, 64) or int(ndim) not in (1, 2):
+            n_dat = 0  # (the C ABI rejects the format)
+        else:
+            n_dat = (raw.numel() * raw.element_size()) // (self.n_pol * int(ndim) * (int(nbit) // 8))
+            if lowcbf:
+                n_dat -= n_dat % 32
+        rows = self.stream_rows(n_dat) if stateful else self.output_length(n_dat)
+        sec, nbytes = self._alloc_section(raw, rows, out_nbit)
+        n_out = c_int64(0)
+        order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
+        fn = self._lib.pfb_filterbank_execute_dada_to_dada if stateful else \
+            self._lib.pfb_analysis_execute_dada_to_dada
+        _lib.check(fn(self._h, c_void_p(raw.data_ptr()), int(nbit), int(ndim), order, n_dat,
+                      c_void_p(sec.data_ptr()), int(out_nbit), float(scale), nbytes, byref(n_out),
+                      _stream_of(raw, self)))
+        return sec[:n_out.value]
+
+    def last_dada_output(self) -> str:
+        """How the plan's last to-DADA call wrote its section: 'fused' (the analysis kernel
+        stored the file's own bytes), 'staged' (the cf32 product packed by a second launch),
+        'none' (no such call, or a cf32-output call since) — pfb_analysis_last_dada_output."""
+        m = int(self._lib.pfb_analysis_last_dada_output(self._h))
+        return {_lib.PFB_DADA_OUTPUT_FUSED: "fused", _lib.PFB_DADA_OUTPUT_STAGED: "staged"}.get(m, "none")
+
 
 # ============================================================================ synthesis
 def _resolve_taper(taper, nf: int, ov: int, spectral_length: int = 0):

@@ -24,7 +24,7 @@ import numpy as np
 from . import layout
 
 __all__ = ["read_header", "write_header", "read_dada_file", "read_dada_raw", "write_dada_file",
-           "write_dada_header", "DADARead", "DADAWrite", "DADAFile", "add_fir_filter_to_header"]
+           "write_dada_section_file", "write_dada_header", "DADARead", "DADAWrite", "DADAFile", "add_fir_filter_to_header"]
 
 _NBIT_NP = {8: np.int8, 16: np.int16, 32: np.float32, 64: np.float64}
 
@@ -205,6 +205,29 @@ def write_dada_file(path, data, hdr: dict, nbit: int = 32) -> dict:
     return h
 
 
+def _section_nbit(section, nbit=None) -> int:
+    """NBIT of an already-packed TFP section (a (n_dat, n_chan, n_pol, 2) tensor of the
+    sample type, as ``AnalysisPlan.execute_to_dada`` returns); checked against ``nbit``."""
+    if section.dim() != 4 or section.shape[3] != 2:
+        raise ValueError("a packed section is (n_dat, n_chan, n_pol, 2)")
+    got = section.element_size() * 8
+    if section.dtype != layout.nbit_dtype(got) or (nbit is not None and int(nbit) != got):
+        raise ValueError(f"section of {section.dtype} does not hold NBIT {nbit if nbit is not None else got} samples")
+    return got
+
+
+def write_dada_section_file(path, section, hdr: dict) -> dict:
+    """``write_dada_file`` for data that are already a packed TFP section (device tensor
+    (n_dat, n_chan, n_pol, 2) of int8 / int16 / float32 / float64): the same header
+    (write_dada_header: NBIT from the sample type, NPOL / NCHAN from the shape), then the
+    section's bytes as they are — no pack launch."""
+    nbit = _section_nbit(section)
+    with open(path, "wb") as f:
+        h = write_dada_header(f, (int(section.shape[2]), int(section.shape[1]), int(section.shape[0])), nbit, hdr)
+        f.write(section.contiguous().cpu().numpy().tobytes())
+    return h
+
+
 class DADARead:
     """DADARead.m:1-85 — streaming reader; ``generate(nsample)`` returns the next
     nsample samples as a (n_pol, n_chan, nsample) complex64 device tensor."""
@@ -274,6 +297,19 @@ class DADAWrite:
         if self._f.tell() == 0:
             write_dada_header(self._f, tuple(data.shape), self.nbit, self.header)
         self._f.write(_pack_to_host(data, self.nbit).tobytes())
+        return self
+
+    def write_section(self, section):
+        """``write`` of data that are already a packed TFP section of the writer's NBIT (a
+        (n_dat, n_chan, n_pol, 2) device tensor, ``AnalysisPlan.execute_to_dada``): header
+        on the first write as ever, then the section's bytes as they are."""
+        _section_nbit(section, self.nbit)
+        if self._f is None:
+            self.open(self.filename)
+        if self._f.tell() == 0:
+            shape = (int(section.shape[2]), int(section.shape[1]), int(section.shape[0]))
+            write_dada_header(self._f, shape, self.nbit, self.header)
+        self._f.write(section.contiguous().cpu().numpy().tobytes())
         return self
 
     def close(self):

@@ -140,6 +140,43 @@ class FilterBank(Channelizer):
             out = _quantize(out, self.rmsOutput, self.device)
         return self, out.transpose(1, 2)
 
+    def execute_to_dada(self, input, nbit: int, scale: float = 1.0):  # noqa: A002
+        """``execute`` of the next chunk (device series) written as a DADA data section:
+        returns ``(self, section)`` with ``section`` the (T_out, n_chan, n_pol, 2) device
+        tensor of int8 / int16 / float32 / float64 samples (TFP order), bit for bit
+        ``layout.dada_pack(float32(scale) * out, nbit)`` of ``execute``'s engine-order
+        output, and the same carry (``AnalysisPlan.execute_to_dada``).  With ``rndInput``,
+        ``rndOutput`` or ``rmsOutput`` configured the quantiser's scale needs the variance of
+        the whole input or output (FilterBank.m:75-83,106-113): the call then takes
+        ``execute`` followed by ``layout.dada_pack``."""
+        if self.rndInput or self.rndOutput or self.rmsOutput:
+            _, view = self.execute(input)
+            return self, self._pack_view(view, nbit, scale)
+        plan = self._ensure_plan(_npol(input))
+        return self, plan.execute_to_dada(input, nbit, scale=scale, stateful=True)
+
+    def execute_dada_to_dada(self, raw, in_nbit: int, out_nbit: int, scale: float = 1.0, ndim: int = 2,
+                             n_pol: int = 1):
+        """``execute_dada`` written as a DADA data section like ``execute_to_dada``: file
+        bytes in, file bytes out (``AnalysisPlan.execute_dada_to_dada``), with the same
+        fallbacks for the quantisation hooks."""
+        if self.rndInput or self.rndOutput or self.rmsOutput:
+            _, view = self.execute_dada(raw, in_nbit, ndim=ndim, n_pol=n_pol)
+            return self, self._pack_view(view, out_nbit, scale)
+        plan = self._ensure_plan(int(n_pol))
+        return self, plan.execute_dada_to_dada(raw, in_nbit, out_nbit, scale=scale, ndim=ndim, stateful=True)
+
+    @staticmethod
+    def _pack_view(view, nbit, scale):
+        """The (n_pol, n_chan, T) view ``execute`` returns -> the scaled, packed section."""
+        import torch
+        buf = view.transpose(1, 2).contiguous()  # engine (n_pol, T, n_chan) order
+        if float(scale) != 1.0:
+            # (per component, in float32: not a complex product)
+            buf = torch.view_as_complex(torch.view_as_real(buf) * float(scale))
+        sec = layout.dada_pack(buf, nbit)
+        return sec.reshape(buf.shape[1], buf.shape[2], buf.shape[0], 2)
+
     def reset(self):
         if self._plan is not None:
             self._plan.reset()

@@ -22,8 +22,7 @@ import numpy as np
 
 from . import dada
 from .config import as_rational
-from .core import (_pfc_view, analysis_plan, polyphase_analysis, polyphase_analysis_padded,
-                   synthesis_plan)
+from .core import analysis_plan, polyphase_analysis, polyphase_analysis_padded, synthesis_plan
 from .firio import read_fir_filter_coeff
 from .window import PFBWindow
 
@@ -78,18 +77,20 @@ def channelize(input_data_file_path: str, channels: int = None, os_factor_str: s
     ch["NCHAN_PFB_0"] = str(int(channels))
     ch["OS_FACTOR"] = f"{os_factor.nu}/{os_factor.de}"
     dada.add_fir_filter_to_header(ch, taps, os_factor)
+    path = os.path.join(output_dir, output_file_name)
     if int(hdr["NCHAN"]) == 1:
-        # the analysis reads the single-channel section's own bytes (no unpacked copy)
+        # the analysis reads the single-channel section's own bytes (no unpacked copy) and
+        # writes the output file's NBIT 32 section itself (no cf32 product, no pack launch)
         name = "polyphase_analysis_padded" if use_padded else "polyphase_analysis"
         plan = analysis_plan(taps, int(channels), os_factor, name, int(hdr["NPOL"]), raw.device.index or 0)
-        chan = _pfc_view(plan.execute_dada(raw, int(hdr["NBIT"]), ndim=int(hdr["NDIM"])))  # (n_pol, channels, K)
+        section = plan.execute_dada_to_dada(raw, int(hdr["NBIT"]), 32, ndim=int(hdr["NDIM"]))
+        dada.write_dada_section_file(path, section, ch)
     else:
         # (channel 1 of a channelised file: unpacked, as read_dada_file does)
         data = dada._matlab_view(dada._unpack(raw, hdr, False))
         fn = polyphase_analysis_padded if use_padded else polyphase_analysis
         chan = fn(data[:, 0, :], taps, int(channels), os_factor)  # (n_pol, channels, K)
-    path = os.path.join(output_dir, output_file_name)
-    dada.write_dada_file(path, chan, ch)
+        dada.write_dada_file(path, chan, ch)
     return dada.DADAFile(path, device).load_data()
 
 
