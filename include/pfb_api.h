@@ -468,6 +468,58 @@ pfb_status pfb_filterbank_execute_dada_to_dada(pfb_analysis_plan* plan, const vo
                                                int64_t out_capacity_bytes, int64_t* n_out, void* stream);
 int32_t pfb_analysis_last_dada_output(const pfb_analysis_plan* plan);
 
+/* Synthesis writing its output straight into a DADA data section (polyphase_synthesis /
+ * InverseFilterBank.m:92-96 followed by write_dada_data.m:32-50): the single-channel TFP
+ * section, NDIM 2, out_nbit 8 / 16 (integers), 32 (float) or 64 (double).  Device memory only.
+ * Output sample t of polarisation p, with P the plan's n_pol, lies at byte
+ * (t * P + p) * 2 * out_nbit / 8 of `out`, re then im — the layout pfb_analysis_execute_dada
+ * reads, so a synthesised section can be fed back to the analysis.  The bytes written, *n_out,
+ * the status codes, pfb_inverse_filterbank_buffered, the sample-offset behaviour and the stream
+ * state are those of the corresponding cf32-output call (pfb_synthesis_execute,
+ * pfb_inverse_filterbank_execute and their _dada twins) into a packed [pol][t] buffer, both
+ * components multiplied by out_scale in float32, followed by pfb_dada_pack at out_nbit with
+ * n_chan = 1, bit for bit.  Exactly samples [0, *n_out) of the section are written and not one
+ * byte beyond.  Every check runs before any launch or state change: a rejected stream call
+ * leaves the carry and the buffered count untouched.  PFB_ERR_INVALID_ARG: a null plan, null
+ * buffers when rows are given or output is due, out_nbit not 8/16/32/64, a non-finite
+ * out_scale, `out` not aligned to one value of out_nbit, and the input-side conditions of the
+ * corresponding call.  PFB_ERR_BUFFER_TOO_SMALL, with nothing written: out_capacity_bytes below
+ * n_out * P * 2 * out_nbit / 8.  Every kind of stream call may alternate on one plan: cf32,
+ * DADA or strided input, cf32 or DADA output.
+ * FUSED: the Nf = 256 wave kernel converts and stores the samples itself, one range-checked
+ * buffer store of 2 / 4 / 8 bytes per complex sample, and the cf32 series never crosses HBM —
+ * out_nbit 8, 16 or 32, `out` aligned to one complex sample, and a plan on that kernel
+ * (input_fft_length 256, input_overlap 48, os 8/7 or 4/3, n_chan a multiple of 16, no spectral
+ * taper).  The input side is the channel IFFT's own launch, so the _dada_to_dada calls read
+ * their section as pfb_synthesis_execute_dada does (pfb_synthesis_last_dada_input reports it)
+ * whatever the output takes.
+ * STAGED: every other plan (input_fft_length 512, the block-kernel shapes, spectral tapers),
+ * out_nbit 64 and an `out` aligned to a value but not to a complex sample run the cf32 path
+ * into a plan-owned buffer, then one scaled pack launch; so these calls accept every plan the
+ * cf32 calls accept.  Chunked synthesis (pfb_synthesis_set_chunk_blocks) works in both.
+ * pfb_synthesis_last_dada_output (enum pfb_dada_output): which of the two the plan's last such
+ * call took, NONE before one or after a cf32-output call, -1 for a null plan.  (Measured A/B
+ * against the pair: DESIGN.md §4.8.) */
+pfb_status pfb_synthesis_execute_to_dada(pfb_synthesis_plan* plan, const pfb_cf32* in,
+                                         int64_t in_pol_stride, int64_t n_dat, int64_t sample_offset,
+                                         void* out, int32_t out_nbit, float out_scale,
+                                         int64_t out_capacity_bytes, int64_t* n_out, void* stream);
+pfb_status pfb_inverse_filterbank_execute_to_dada(pfb_synthesis_plan* plan, const pfb_cf32* in,
+                                                  int64_t in_pol_stride, int64_t n_in, void* out,
+                                                  int32_t out_nbit, float out_scale,
+                                                  int64_t out_capacity_bytes, int64_t* n_out, void* stream);
+pfb_status pfb_synthesis_execute_dada_to_dada(pfb_synthesis_plan* plan, const void* in, int32_t nbit,
+                                              int32_t ndim, int32_t order, int64_t n_dat,
+                                              int64_t sample_offset, void* out, int32_t out_nbit,
+                                              float out_scale, int64_t out_capacity_bytes, int64_t* n_out,
+                                              void* stream);
+pfb_status pfb_inverse_filterbank_execute_dada_to_dada(pfb_synthesis_plan* plan, const void* in,
+                                                       int32_t nbit, int32_t ndim, int32_t order,
+                                                       int64_t n_in, void* out, int32_t out_nbit,
+                                                       float out_scale, int64_t out_capacity_bytes,
+                                                       int64_t* n_out, void* stream);
+int32_t pfb_synthesis_last_dada_output(const pfb_synthesis_plan* plan);
+
 /* The synthesis calls reading their channelised rows strided (device memory only): channel c
  * of row t of polarisation p is in[p * in_pol_stride + t * in_row_stride + c * in_chan_stride]
  * — the input-side mirror of pfb_filterbank_execute_strided.  Polarisations may interleave

@@ -14,6 +14,9 @@ one MI355X, as algorithmic HBM bytes / time against the 8 TB/s peak.
   * --only-dada-output: analysis into a DADA section (C2, LowCBF, SKA-Mid stage 1), the pair
     (execute, scale, pfb_dada_pack) against pfb_analysis_execute_to_dada /
     pfb_analysis_execute_dada_to_dada, interleaved
+  * --only-dada-synthesis-output: synthesis into a DADA section at the C2 shape, the pair
+    (pfb_synthesis_execute[_dada], scale, pfb_dada_pack) against pfb_synthesis_execute_to_dada /
+    pfb_synthesis_execute_dada_to_dada, interleaved, and the cf32 synthesis alone
   * --only-twostage-inverse: TwoStageInverseFilterBank with the channel gather against the
     strided input (pfb_inverse_filterbank_execute_strided), interleaved
 
@@ -63,6 +66,8 @@ def main():
                     help="the dada_analysis A/B alone (--reps: calls per timed window)")
     ap.add_argument("--only-dada-output", action="store_true",
                     help="the dada_output A/B alone (--reps: calls per timed window)")
+    ap.add_argument("--only-dada-synthesis-output", action="store_true",
+                    help="the dada_synthesis_output A/B alone (--reps: calls per timed window)")
     ap.add_argument("--only-twostage-inverse", action="store_true",
                     help="the inverse cascade's gather vs strided-input A/B alone (--reps: calls per window)")
     ap.add_argument("--rounds", type=int, default=15,
@@ -103,6 +108,8 @@ def main():
         return dada_analysis(torch, pfb, dev, max(args.reps, 20), args.rounds)
     if args.only_dada_output:
         return dada_output(torch, pfb, dev, max(args.reps, 20), args.rounds)
+    if args.only_dada_synthesis_output:
+        return dada_synthesis_output(torch, pfb, dev, max(args.reps, 20), args.rounds)
     if args.only_twostage_inverse:
         return twostage_inverse(torch, pfb, noise, max(args.reps, 20), max(args.rounds, 5))
     # ---- C2' (4/3) round trip
@@ -458,6 +465,120 @@ def dada_output(torch, pfb, dev, reps, rounds):
             "B_bytes": int(n_pol * (n * esz_in + (K * C * esz if path == "fused" else 2 * prod + K * C * esz)))}),
             flush=True)
         del plan, src, cf, scaled, sec_a, sec_b
+        torch.cuda.empty_cache()
+
+
+def dada_synthesis_output(torch, pfb, dev, reps, rounds):
+    """Channelised rows -> single-channel DADA section (TFP, NBIT 8 / 16 / 32) at the C2 synthesis
+    shape (256 ch, 8/7, Nf 256, Ov 48, tukey, deripple; the rows of a 2^24-sample unit).  A: the
+    pair a caller had before — the cf32-output call (pfb_synthesis_execute, or
+    pfb_synthesis_execute_dada for an NBIT 16 section), both components times the scale in
+    float32 (one elementwise pass), then pfb_dada_pack with one channel.  B:
+    pfb_synthesis_execute_to_dada / pfb_synthesis_execute_dada_to_dada.  Both through the C ABI
+    into preallocated buffers.  The sections are asserted equal first; then `rounds` windows of
+    `reps` calls of each side, alternating A and B in one process, after a warm-up of both.  One
+    line per case with the median, min, max and quartiles of each side's per-call time, and
+    A_execute_ms: the cf32-output call alone, timed in windows of its own between the two.
+    stays_fused: B's median lies below A's by more than A's min-to-max spread (and the larger of
+    the two interquartile spreads)."""
+    from ctypes import byref, c_int64, c_void_p
+    from ska_pst_dsp_model_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator(device=dev).manual_seed(6)
+    N, rows = 256, ((1 << 24) // 224) // 32 * 32
+    taps = pfb.design_PFB_FIR_filter(N, "8/7", 12)
+    win = pfb.PFBWindow().lookup["tukey"](256, 48)
+    dts = {8: torch.int8, 16: torch.int16, 32: torch.float32}
+    for n_pol in (1, 2):
+        plan = pfb.SynthesisPlan(N, "8/7", 256, 48, True, 1, True, taps, win, None, n_pol)
+        n_o = plan.output_length(rows)
+        cf = torch.empty((n_pol, n_o), dtype=torch.complex64, device=dev)
+        scaled = torch.empty_like(cf)
+        for in_nbit in (0, 16):
+            if in_nbit:
+                src = torch.randint(-(1 << 15), 1 << 15, (rows * N * n_pol * 2,), dtype=torch.int16, device=dev,
+                                    generator=g)
+            else:
+                src = torch.view_as_complex(torch.randn((n_pol, rows, N, 2), device=dev, generator=g))
+            stream = c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            n_out = c_int64(0)
+
+            def execute_cf32():
+                if in_nbit:
+                    _lib.check(lib.pfb_synthesis_execute_dada(plan._h, c_void_p(src.data_ptr()), in_nbit, 2,
+                                                              _lib.PFB_DADA_TFP, rows, 1, c_void_p(cf.data_ptr()), n_o,
+                                                              n_o, byref(n_out), stream))
+                else:
+                    _lib.check(lib.pfb_synthesis_execute(plan._h, c_void_p(src.data_ptr()), rows * N, rows, 1,
+                                                         c_void_p(cf.data_ptr()), n_o, n_o, byref(n_out),
+                                                         _lib.PFB_MEM_DEVICE, stream))
+
+            # the series' component rms at a third of the integer range (0.37 for NBIT 32)
+            execute_cf32()
+            rms = float(torch.view_as_real(cf).square().mean().sqrt())
+            for nbit in (8, 16, 32):
+                scale = float(np.float32((((1 << (nbit - 1)) - 1) / 3.0 if nbit != 32 else 0.37) / rms))
+                sec_a = torch.empty((n_o, 1, n_pol, 2), dtype=dts[nbit], device=dev)
+                sec_b = torch.empty_like(sec_a)
+                nbytes = sec_b.numel() * sec_b.element_size()
+
+                def side_a():
+                    execute_cf32()
+                    torch.mul(torch.view_as_real(cf), scale, out=torch.view_as_real(scaled))
+                    _lib.check(lib.pfb_dada_pack(c_void_p(scaled.data_ptr()), n_o, n_o, 1, n_pol,
+                                                 c_void_p(sec_a.data_ptr()), nbit, stream))
+
+                def side_b():
+                    if in_nbit:
+                        _lib.check(lib.pfb_synthesis_execute_dada_to_dada(
+                            plan._h, c_void_p(src.data_ptr()), in_nbit, 2, _lib.PFB_DADA_TFP, rows, 1,
+                            c_void_p(sec_b.data_ptr()), nbit, scale, nbytes, byref(n_out), stream))
+                    else:
+                        _lib.check(lib.pfb_synthesis_execute_to_dada(
+                            plan._h, c_void_p(src.data_ptr()), rows * N, rows, 1, c_void_p(sec_b.data_ptr()), nbit,
+                            scale, nbytes, byref(n_out), stream))
+
+                side_a()
+                side_b()
+                path_in, path = plan.last_dada_input(), plan.last_dada_output()
+                torch.cuda.synchronize()
+                assert n_out.value == n_o and torch.equal(sec_a, sec_b), \
+                    f"dada_synthesis_output {in_nbit}->{nbit} {n_pol} pol: sections differ"
+                for _ in range(2):
+                    timeit(torch, side_a, reps)
+                    timeit(torch, side_b, reps)
+                ta, tb, tc = [], [], []
+                for _ in range(rounds):
+                    ta.append(timeit(torch, side_a, reps))
+                    tb.append(timeit(torch, side_b, reps))
+                    tc.append(timeit(torch, execute_cf32, reps))
+
+                def stats(t):
+                    q = np.percentile(t, [0, 25, 50, 75, 100])
+                    return {k: round(float(v), 4) for k, v in zip(("min", "q25", "median", "q75", "max"), q)}
+                a, b, c = stats(ta), stats(tb), stats(tc)
+                iqr_a, iqr_b = a["q75"] - a["q25"], b["q75"] - b["q25"]
+                spread_a = a["max"] - a["min"]
+                esz_in, esz = (2 * in_nbit // 8 if in_nbit else 8), 2 * nbit // 8
+                print(json.dumps({
+                    "kernel": "dada_synthesis_output", "shape": "256ch 8/7 Nf256 Ov48 tukey deripple", "rows": rows,
+                    "n_out": n_o, "n_pol": n_pol, "in": f"nbit{in_nbit}" if in_nbit else "cf32", "nbit": nbit,
+                    "path": path, "input_path": path_in, "calls_per_window": reps, "windows": rounds,
+                    "outputs_equal": True, "A_execute_scale_pack_ms": a, "B_execute_to_dada_ms": b,
+                    "A_execute_ms": c, "A_iqr_ms": round(iqr_a, 4), "B_iqr_ms": round(iqr_b, 4),
+                    "A_spread_ms": round(spread_a, 4),
+                    "B_below_A_by_ms": round(a["median"] - b["median"], 4),
+                    "B_over_A": round(b["median"] / a["median"], 4),
+                    "stays_fused": bool(path == "fused" and
+                                        a["median"] - b["median"] > max(spread_a, iqr_a, iqr_b)),
+                    # per call beyond the channel IFFT: A writes the series, reads and rewrites it
+                    # scaled, reads it again and writes the section; B writes the section
+                    "A_output_bytes": int(n_pol * n_o * (4 * 8 + esz)),
+                    "B_output_bytes": int(n_pol * n_o * (esz if path == "fused" else 2 * 8 + esz)),
+                    "input_bytes": int(n_pol * rows * N * esz_in)}), flush=True)
+                del sec_a, sec_b
+            del src
+        del plan, cf, scaled
         torch.cuda.empty_cache()
 
 

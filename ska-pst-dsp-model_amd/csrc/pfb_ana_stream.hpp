@@ -2,6 +2,7 @@
 // analysis_stream_kernel (instantiated in pfb_analysis.hip).
 #pragma once
 #include "pfb_common.hpp"
+#include "pfb_dada_store.hpp"
 #include "pfb_sample.hpp"
 
 namespace pfb {
@@ -89,38 +90,10 @@ struct InDada8 {  // NBIT 8: int8 (re, im)
   }
 };
 
-// The store side of the same kernel (analysis_stream_body's OUT).  OutCf32: the packed
-// [pol][k][c] complex float32 rows (BufRowStore / LcbfRowStore and the strided stores).
-// OutDada8 / 16 / 32: a TFP DADA section, NDIM 2 (AnalysisArgs::dout) — kBytes per complex
-// sample, (re, im) converted by pfb_dada_pack's to_sample and written by one range-checked
-// buffer store (cache policy kAuxDadaOut).
-struct OutCf32 {
-  static constexpr bool kDada = false;
-};
-struct OutDada32 {  // NBIT 32: float (re, im)
-  static constexpr bool kDada = true;
-  static constexpr int kBytes = 8;
-  static __device__ __forceinline__ void store(__amdgpu_buffer_rsrc_t r, uint32_t off, float re, float im) {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v2f{to_sample<float>(re), to_sample<float>(im)}),
-                                          r, off, 0, kAuxDadaOut);
-  }
-};
-struct OutDada16 {  // NBIT 16: int16 (re, im)
-  static constexpr bool kDada = true;
-  static constexpr int kBytes = 4;
-  static __device__ __forceinline__ void store(__amdgpu_buffer_rsrc_t r, uint32_t off, float re, float im) {
-    const uint32_t w = (uint32_t)(uint16_t)to_sample<int16_t>(re) | ((uint32_t)(uint16_t)to_sample<int16_t>(im) << 16);
-    __builtin_amdgcn_raw_buffer_store_b32(w, r, off, 0, kAuxDadaOut);
-  }
-};
-struct OutDada8 {  // NBIT 8: int8 (re, im)
-  static constexpr bool kDada = true;
-  static constexpr int kBytes = 2;
-  static __device__ __forceinline__ void store(__amdgpu_buffer_rsrc_t r, uint32_t off, float re, float im) {
-    const uint16_t w = (uint16_t)((uint16_t)(uint8_t)to_sample<int8_t>(re) | ((uint16_t)(uint8_t)to_sample<int8_t>(im) << 8));
-    __builtin_amdgcn_raw_buffer_store_b16(w, r, off, 0, kAuxDadaOut);
-  }
-};
+// The store side of the same kernel (analysis_stream_body's OUT; pfb_dada_store.hpp).  OutCf32:
+// the packed [pol][k][c] complex float32 rows (BufRowStore / LcbfRowStore and the strided
+// stores).  OutDada8 / 16 / 32: a TFP DADA section, NDIM 2 (AnalysisArgs::dout), through
+// DadaRowStore (cache policy kAuxDadaOut).
 
 // Rows [k0, k0 + T) of a DADA section of C channels and P polarisations, polarisation `pol`
 // (BufRowStore's twin; LCBF: LcbfRowStore's bin -> channel map and drop rule, C = 216): FFT bin

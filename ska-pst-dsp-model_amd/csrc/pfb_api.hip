@@ -1198,6 +1198,12 @@ struct pfb_synthesis_plan {
   int last_stage1 = 0;           // pfb_synthesis_last_stage1_rows: where the last launch got its rows
   int last_dada = PFB_DADA_INPUT_NONE;  // pfb_synthesis_last_dada_input
   int last_strided = PFB_STRIDED_INPUT_NONE;  // pfb_synthesis_last_strided_input
+  int last_dada_out = PFB_DADA_OUTPUT_NONE;   // pfb_synthesis_last_dada_output
+  // set for the duration of a FUSED to-DADA call (synthesis_to_dada): every block launch of the
+  // call stores into this section instead of its cf32 output (SynthBlockArgs::dout)
+  void* dout = nullptr;
+  int dout_nbit = 0;
+  float dout_scale = 1.f;
   int rt_chunk_blocks = 64;  // round-trip pipeline chunk (PFB_RT_CHUNK_BLOCKS)
   int timing_mask = 0;  // PFB_TIMING_MASK (timing experiments; results invalid when set)
   int ranges = -1;  // PFB_SYNTH_RANGES: 0 one workgroup per block, -1 persistent auto, >0 persistent
@@ -1417,6 +1423,9 @@ static pfb::SynthBlockArgs synth_args(const pfb_synthesis_plan* p, const float2*
   a.xcd = p->xcd;
   a.timing_mask = p->timing_mask;
   a.zblk = zblk;
+  a.dout = p->dout;
+  a.dout_nbit = p->dout_nbit;
+  a.dout_scale = p->dout_scale;
   return a;
 }
 
@@ -1918,11 +1927,18 @@ static pfb_status synthesis_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int6
   return PFB_OK;
 }
 
+// a cf32-output call that went through: pfb_synthesis_last_dada_output reports NONE again
+static pfb_status cf32_output(pfb_synthesis_plan* p, pfb_status st) {
+  if (p && st == PFB_OK) p->last_dada_out = PFB_DADA_OUTPUT_NONE;
+  return st;
+}
+
 pfb_status pfb_synthesis_execute(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
                                  int64_t n_dat, int64_t sample_offset, pfb_cf32* out,
                                  int64_t out_ps, int64_t cap, int64_t* n_out, int32_t mem,
                                  void* stream) {
-  return synthesis_exec(p, in, in_ps, nullptr, n_dat, sample_offset, out, out_ps, cap, n_out, mem, stream);
+  return cf32_output(
+      p, synthesis_exec(p, in, in_ps, nullptr, n_dat, sample_offset, out, out_ps, cap, n_out, mem, stream));
 }
 
 pfb_status pfb_synthesis_execute_dada(pfb_synthesis_plan* p, const void* in, int32_t nbit, int32_t ndim,
@@ -1931,8 +1947,8 @@ pfb_status pfb_synthesis_execute_dada(pfb_synthesis_plan* p, const void* in, int
   const DadaSection sec{in, nbit, ndim, order};
   const pfb_status st = dada_section_check(p, sec, n_dat);
   if (st != PFB_OK) return st;
-  return synthesis_exec(p, nullptr, 0, &sec, n_dat, sample_offset, out, out_ps, cap, n_out, PFB_MEM_DEVICE,
-                        stream);
+  return cf32_output(p, synthesis_exec(p, nullptr, 0, &sec, n_dat, sample_offset, out, out_ps, cap, n_out,
+                                       PFB_MEM_DEVICE, stream));
 }
 
 int32_t pfb_synthesis_last_dada_input(const pfb_synthesis_plan* p) { return p ? p->last_dada : -1; }
@@ -1942,8 +1958,8 @@ pfb_status pfb_synthesis_execute_strided(pfb_synthesis_plan* p, const pfb_cf32* 
                                          int64_t sample_offset, pfb_cf32* out, int64_t out_ps, int64_t cap,
                                          int64_t* n_out, void* stream) {
   const StridedView sv{in_ps, in_rs, in_cs, in_cap};
-  return synthesis_exec(p, in, in_ps, nullptr, n_dat, sample_offset, out, out_ps, cap, n_out, PFB_MEM_DEVICE,
-                        stream, &sv);
+  return cf32_output(p, synthesis_exec(p, in, in_ps, nullptr, n_dat, sample_offset, out, out_ps, cap, n_out,
+                                       PFB_MEM_DEVICE, stream, &sv));
 }
 
 int32_t pfb_synthesis_last_strided_input(const pfb_synthesis_plan* p) { return p ? p->last_strided : -1; }
@@ -1968,6 +1984,30 @@ pfb_status pfb_inverse_filterbank_set_sample_offset(pfb_synthesis_plan* p, int64
 // blocks of new rows read through the layout where the channel IFFT can, the stitched head
 // and the carry are copied out of it by the strided-rows copy kernel; otherwise the rows are
 // copied whole once every check has passed, and the cf32 path runs.)
+// The lengths of a stream call of n_in new rows on the plan's current state
+struct IfbLens {
+  int64_t total, so, B, input_idat, buffered, olen;
+};
+static IfbLens ifb_lens(const pfb_synthesis_plan* p, int64_t n_in) {
+  IfbLens l{};
+  l.total = p->buffered + n_in;
+  l.so = std::min(p->ifb_offset, l.total);  // in(:, :, sample_offset:end)
+  // output length and carry-over rounded up to a multiple of nu (InverseFilterBank.m:104-135)
+  l.B = synth_blocks(p, l.total - l.so);
+  const int64_t full = l.B * p->Lkeep;
+  l.input_idat = l.B * p->keep;
+  l.buffered = l.total - l.input_idat;
+  l.olen = full;
+  const int64_t rem = ((l.buffered % p->nu) + p->nu) % p->nu;
+  if (rem != 0) {
+    l.buffered += p->nu - rem;
+    l.input_idat = l.total - l.buffered;
+    // output_ndat = input_idat * (n_chan de)/nu, used as a Matlab colon end (floor)
+    l.olen = std::min(std::max<int64_t>(0, floordiv(l.input_idat * p->N * p->de, p->nu)), full);
+  }
+  return l;
+}
+
 static pfb_status ifb_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps, const DadaSection* sec,
                            int64_t n_in, pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
                            int32_t mem, void* stream, const StridedView* sv = nullptr) {
@@ -1983,22 +2023,10 @@ static pfb_status ifb_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in
   p->last_strided = PFB_STRIDED_INPUT_NONE;
   hipStream_t s = (hipStream_t)stream;
   const int N = p->N;
-  const int64_t total = p->buffered + n_in;
   const hipMemcpyKind kin = mem == PFB_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  const int64_t so = std::min(p->ifb_offset, total);  // in(:, :, sample_offset:end)
-  // output length and carry-over rounded up to a multiple of nu (InverseFilterBank.m:104-135)
-  const int64_t B = synth_blocks(p, total - so);
-  const int64_t full = B * p->Lkeep;
-  int64_t input_idat = B * p->keep;
-  int64_t buffered = total - input_idat;
-  int64_t olen = full;
-  const int64_t rem = ((buffered % p->nu) + p->nu) % p->nu;
-  if (rem != 0) {
-    buffered += p->nu - rem;
-    input_idat = total - buffered;
-    // output_ndat = input_idat * (n_chan de)/nu, used as a Matlab colon end (floor)
-    olen = std::min(std::max<int64_t>(0, floordiv(input_idat * N * p->de, p->nu)), full);
-  }
+  const IfbLens len = ifb_lens(p, n_in);
+  const int64_t total = len.total, so = len.so, B = len.B, input_idat = len.input_idat, buffered = len.buffered,
+                olen = len.olen;
   if (input_idat < 0)
     // no complete block and a carry rounded up past the data: InverseFilterBank.m:104-122
     // would index input(:, :, input_idat + 1 : end) before the first sample (its rounding
@@ -2143,7 +2171,7 @@ static pfb_status ifb_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in
 pfb_status pfb_inverse_filterbank_execute(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
                                           int64_t n_in, pfb_cf32* out, int64_t out_ps, int64_t cap,
                                           int64_t* n_out, int32_t mem, void* stream) {
-  return ifb_exec(p, in, in_ps, nullptr, n_in, out, out_ps, cap, n_out, mem, stream);
+  return cf32_output(p, ifb_exec(p, in, in_ps, nullptr, n_in, out, out_ps, cap, n_out, mem, stream));
 }
 
 pfb_status pfb_inverse_filterbank_execute_dada(pfb_synthesis_plan* p, const void* in, int32_t nbit,
@@ -2152,7 +2180,7 @@ pfb_status pfb_inverse_filterbank_execute_dada(pfb_synthesis_plan* p, const void
   const DadaSection sec{in, nbit, ndim, order};
   const pfb_status st = dada_section_check(p, sec, n_in);
   if (st != PFB_OK) return st;
-  return ifb_exec(p, nullptr, 0, &sec, n_in, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream);
+  return cf32_output(p, ifb_exec(p, nullptr, 0, &sec, n_in, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream));
 }
 
 pfb_status pfb_inverse_filterbank_execute_strided(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
@@ -2160,8 +2188,131 @@ pfb_status pfb_inverse_filterbank_execute_strided(pfb_synthesis_plan* p, const p
                                                   pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
                                                   void* stream) {
   const StridedView sv{in_ps, in_rs, in_cs, in_cap};
-  return ifb_exec(p, in, in_ps, nullptr, n_in, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream, &sv);
+  return cf32_output(p, ifb_exec(p, in, in_ps, nullptr, n_in, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream, &sv));
 }
+
+// the wave kernel stores such a section itself (pfb_api.h, FUSED).  Every (polarisations, NBIT)
+// cell stays FUSED: on the C2 synthesis unit each takes 0.49-0.73 of the time of the pair
+// (execute, scale, pfb_dada_pack), the gap 0.085-0.177 ms against a run-to-run spread of the
+// pair of at most 0.006 ms — cf32 rows into NBIT 8 / 16 / 32: one polarisation 0.115 / 0.119 /
+// 0.129 against 0.211 / 0.220 / 0.227 ms, two 0.229 / 0.253 / 0.320 against 0.406 / 0.420 /
+// 0.436 ms (the narrowest cell, 0.73); from an NBIT 16 section 0.099 / 0.099 / 0.100 against
+// 0.198 / 0.184 / 0.205 and 0.202 / 0.220 / 0.284 against 0.378 / 0.391 / 0.409 ms
+// (profiles/dada_synthesis_output_ab.jsonl)
+static bool synthesis_dada_out_fusable(const pfb_synthesis_plan* p, const void* out, int nbit) {
+  if (nbit != 8 && nbit != 16 && nbit != 32) return false;
+  if (p->has_spectral || reinterpret_cast<uintptr_t>(out) % (size_t)(nbit / 4) != 0) return false;
+  // (the stage-1 row layout synthesis_chunk picks for the wave kernel: 2-row runs)
+  return pfb::synth_wave_dadaout_supported(synth_args(p, nullptr, 0, 0, 1, nullptr, 0, 0, 2), nbit);
+}
+
+// The to-DADA calls (pfb_api.h): every check here — the callee's own, in its order, among
+// them — before the callee launches or changes the stream state; then FUSED — the plan's block
+// launches store the section (pfb_synthesis_plan::dout) — or STAGED — the cf32 path into the
+// plan's buffer and the scaled pack launch.
+static pfb_status synthesis_to_dada(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
+                                    const DadaSection* sec, int64_t n, int64_t sample_offset, void* out,
+                                    int32_t nbit, float scale, int64_t cap_bytes, int64_t* n_out, void* stream,
+                                    bool stream_call) {
+  if (!p) return fail(PFB_ERR_INVALID_ARG, "null plan");
+  if (nbit != 8 && nbit != 16 && nbit != 32 && nbit != 64)
+    return fail(PFB_ERR_INVALID_ARG, "output NBIT must be 8, 16, 32 or 64");
+  if (!std::isfinite(scale)) return fail(PFB_ERR_INVALID_ARG, "output scale is not finite");
+  if (reinterpret_cast<uintptr_t>(out) % (size_t)(nbit / 8) != 0)
+    return fail(PFB_ERR_INVALID_ARG, "output section not aligned to its NBIT");
+  // the input-side conditions of the corresponding cf32-output call
+  if (sec) {
+    const pfb_status st = dada_section_check(p, *sec, n);
+    if (st != PFB_OK) return st;
+  }
+  if (!(sec ? sec->base : (const void*)in) && n > 0) return fail(PFB_ERR_INVALID_ARG, "null argument");
+  if (!stream_call && sample_offset < 1) return fail(PFB_ERR_INVALID_ARG, "sample_offset is 1-based (>= 1)");
+  if (n < 0) return fail(PFB_ERR_INVALID_ARG, "negative row count");
+  int64_t olen;
+  if (stream_call) {
+    const IfbLens len = ifb_lens(p, n);
+    if (len.input_idat < 0)
+      return fail(PFB_ERR_INVALID_ARG,
+                  "InverseFilterBank: %lld buffered + %lld new rows hold no complete block and "
+                  "round the carry past the data (InverseFilterBank.m:104-122); pass more rows",
+                  (long long)p->buffered, (long long)n);
+    olen = len.olen;
+  } else {
+    const int64_t off = std::min<int64_t>(sample_offset - 1, n);
+    olen = synth_blocks(p, n - off) * p->Lkeep;
+  }
+  if (n_out) *n_out = olen;
+  const int64_t need = olen * p->n_pol * 2 * (nbit / 8);
+  if (stream_call) {  // (pfb_inverse_filterbank_execute's order)
+    if (cap_bytes < need)
+      return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld bytes", (long long)cap_bytes,
+                  (long long)need);
+    if (!sec && in_ps < n * p->N) return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
+    if (olen > 0 && !out) return fail(PFB_ERR_INVALID_ARG, "null output");
+  } else if (olen > 0) {  // (pfb_synthesis_execute's; a call that yields nothing checks no more)
+    if (!out) return fail(PFB_ERR_INVALID_ARG, "null output");
+    if (cap_bytes < need)
+      return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld bytes", (long long)cap_bytes,
+                  (long long)need);
+    if (!sec && in_ps < n * p->N) return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
+  }
+  HIPCHK(hipSetDevice(p->device));
+  const bool fused = synthesis_dada_out_fusable(p, out, nbit);
+  pfb_cf32* o;
+  if (fused) {
+    // (`out` stands in for the cf32 buffer in the callee's null, capacity and stride checks;
+    // the block launches write through the plan's dout only)
+    o = static_cast<pfb_cf32*>(out);
+    p->dout = out;
+    p->dout_nbit = nbit;
+    p->dout_scale = scale;
+  } else {
+    HIPCHK(p->stage_out.ensure((size_t)p->n_pol * std::max<int64_t>(olen, 1) * sizeof(float2)));
+    o = p->stage_out.as<pfb_cf32>();
+  }
+  const pfb_status st =
+      stream_call ? ifb_exec(p, in, in_ps, sec, n, o, olen, olen, n_out, PFB_MEM_DEVICE, stream)
+                  : synthesis_exec(p, in, in_ps, sec, n, sample_offset, o, olen, olen, n_out, PFB_MEM_DEVICE, stream);
+  p->dout = nullptr;
+  if (st != PFB_OK) return st;
+  if (!fused && olen > 0)
+    HIPCHK(pfb::launch_dada_pack_scaled(p->stage_out.as<float2>(), olen, olen, 1, p->n_pol, out, nbit, scale,
+                                        (hipStream_t)stream));
+  p->last_dada_out = fused ? PFB_DADA_OUTPUT_FUSED : PFB_DADA_OUTPUT_STAGED;
+  return PFB_OK;
+}
+
+pfb_status pfb_synthesis_execute_to_dada(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps, int64_t n_dat,
+                                         int64_t sample_offset, void* out, int32_t out_nbit, float out_scale,
+                                         int64_t cap_bytes, int64_t* n_out, void* stream) {
+  return synthesis_to_dada(p, in, in_ps, nullptr, n_dat, sample_offset, out, out_nbit, out_scale, cap_bytes, n_out,
+                           stream, false);
+}
+
+pfb_status pfb_inverse_filterbank_execute_to_dada(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
+                                                  int64_t n_in, void* out, int32_t out_nbit, float out_scale,
+                                                  int64_t cap_bytes, int64_t* n_out, void* stream) {
+  return synthesis_to_dada(p, in, in_ps, nullptr, n_in, 1, out, out_nbit, out_scale, cap_bytes, n_out, stream, true);
+}
+
+pfb_status pfb_synthesis_execute_dada_to_dada(pfb_synthesis_plan* p, const void* in, int32_t nbit, int32_t ndim,
+                                              int32_t order, int64_t n_dat, int64_t sample_offset, void* out,
+                                              int32_t out_nbit, float out_scale, int64_t cap_bytes, int64_t* n_out,
+                                              void* stream) {
+  const DadaSection sec{in, nbit, ndim, order};
+  return synthesis_to_dada(p, nullptr, 0, &sec, n_dat, sample_offset, out, out_nbit, out_scale, cap_bytes, n_out,
+                           stream, false);
+}
+
+pfb_status pfb_inverse_filterbank_execute_dada_to_dada(pfb_synthesis_plan* p, const void* in, int32_t nbit,
+                                                       int32_t ndim, int32_t order, int64_t n_in, void* out,
+                                                       int32_t out_nbit, float out_scale, int64_t cap_bytes,
+                                                       int64_t* n_out, void* stream) {
+  const DadaSection sec{in, nbit, ndim, order};
+  return synthesis_to_dada(p, nullptr, 0, &sec, n_in, 1, out, out_nbit, out_scale, cap_bytes, n_out, stream, true);
+}
+
+int32_t pfb_synthesis_last_dada_output(const pfb_synthesis_plan* p) { return p ? p->last_dada_out : -1; }
 
 int64_t pfb_inverse_filterbank_buffered(const pfb_synthesis_plan* p) { return p ? p->buffered : -1; }
 

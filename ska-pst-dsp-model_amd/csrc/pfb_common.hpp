@@ -65,6 +65,16 @@ constexpr int kAuxLcbf = PFB_AUX_LCBF;
 #define PFB_AUX_DADAOUT 0
 #endif
 constexpr int kAuxDadaOut = PFB_AUX_DADAOUT;
+// DADA sections stored by the Nf = 256 wave synthesis (synth_wave_dadaout_kernel): the default
+// policy.  The same trade as above, measured on the C2 synthesis unit, cf32 rows in
+// (profiles/dada_synthesis_output_policy_ab.jsonl; default / nontemporal, ms per call): one
+// polarisation NBIT 8 0.115 / 0.116, 16 0.119 / 0.113, 32 0.129 / 0.107; two polarisations,
+// each line half-filled by either workgroup, NBIT 8 0.229 / 0.261, 16 0.253 / 0.287, 32 0.320 /
+// 0.390.  One constant: nontemporal gains 5 and 17 % in two cells and loses 14-22 % in three.
+#ifndef PFB_AUX_SYNDADAOUT
+#define PFB_AUX_SYNDADAOUT 0
+#endif
+constexpr int kAuxSynDadaOut = PFB_AUX_SYNDADAOUT;
 // the same for the C3 (SKA-Mid, N > 256) kernels' streams, nontemporal (1) or default (0):
 // the FIR's stage-1 rows (PFB_NT_FIRZ), the row FFT's rows (RowStore, PFB_NT_ROW), the
 // synth_wave512 output (PFB_NT_W5).  Measured: the C3 round trip 0.960/0.967 -> 0.936/0.954

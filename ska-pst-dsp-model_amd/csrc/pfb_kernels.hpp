@@ -246,6 +246,17 @@ struct SynthBlockArgs {
   const float* fir_g;
   int64_t fir_q0;
   int fir_nu, fir_de, fir_pe;
+  // The output goes out as a single-channel DADA data section instead of `out`
+  // (pfb_synthesis_execute_to_dada; synth_wave_dadaout_supported): TFP order, NDIM 2,
+  // dout_nbit 8 / 16 (integers) or 32 (float); sample t of polarisation p at byte
+  // (t n_pol + p) dout_nbit / 4 of dout, its value to_sample(dout_scale * y) per component of
+  // the y the cf32 kernel stores.  dout is aligned to one complex sample and is the section of
+  // the whole call (block0 counts from its sample 0); `out` and out_pol_stride are unused.
+  // (Placed so that `linear` stays the struct's last word: the wave kernels fetch it together
+  // with the launch's grid size, which follows the struct in the kernel arguments.)
+  int dout_nbit = 0;
+  void* dout = nullptr;
+  float dout_scale = 1.f;
   // wave kernels: workgroup -> (block range, phase group) order, 0 XCD-aware (xcd_tile), 1
   // linear (blockIdx.x: consecutive workgroups are the phase groups of one block range)
   int linear = 0;
@@ -329,6 +340,10 @@ bool synth_wave_supported(const SynthBlockArgs& a);
 // the same kernel with recomputed stage-1 rows (SynthBlockArgs::fir_x)
 bool synth_wave_fir_supported(const SynthBlockArgs& a);
 hipError_t launch_synth_wave(const SynthBlockArgs& a, hipStream_t s);
+// the same kernel (stored stage-1 rows, kept-register stores) writing a DADA section of `nbit`
+// (SynthBlockArgs::dout; pfb_synth_wave_dadaout.hip); launch_synth_block takes it when dout is set
+bool synth_wave_dadaout_supported(const SynthBlockArgs& a, int nbit);
+hipError_t launch_synth_wave_dadaout(const SynthBlockArgs& a, hipStream_t s);
 // Nf = 512, W = 448, keep 256 (SKA-Mid): one output phase per 32 lanes (pfb_synth_wave512.hip)
 bool synth_wave512_supported(const SynthBlockArgs& a);
 hipError_t launch_synth_wave512(const SynthBlockArgs& a, hipStream_t s);

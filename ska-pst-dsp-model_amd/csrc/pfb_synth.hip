@@ -235,6 +235,9 @@ bool synth_block_supported(int Nf, int W) {
 
 hipError_t launch_synth_block(const SynthBlockArgs& a, hipStream_t s) {
   if (a.n_blocks <= 0) return hipSuccess;
+  // a DADA section as the output: the Nf = 256 wave kernel's DADA store, or an error (no other
+  // kernel writes one — the caller stages those plans through the cf32 output)
+  if (a.dout) return launch_synth_wave_dadaout(a, s);
   // SKA-Mid shape (Nf 512, W 448, Ov 128): the wave kernel, on rows or 2-row runs (zblk 2)
   // (PFB_SYNTH_WAVE512=0: the block kernel, experiments build — synth_wave512_supported)
   if (a.Nf == 512 && synth_wave512_supported(a)) return launch_synth_wave512(a, s);

@@ -1,7 +1,9 @@
 // pfb_synth_wave.hpp — synthesis stage 2 for Nf = 256 with one output phase per 16 lanes
-// (the algorithm: pfb_synth_wave.hip), instantiated by synth_wave_kernel.
+// (the algorithm: pfb_synth_wave.hip), instantiated by synth_wave_kernel and, with a DADA
+// store, by synth_wave_dadaout_kernel (pfb_synth_wave_dadaout.hip).
 #pragma once
 #include "pfb_common.hpp"
+#include "pfb_dada_store.hpp"
 
 namespace pfb {
 
@@ -144,8 +146,11 @@ struct RangeSched {
 //      block b + 1, right after its first barrier, from registers reserved until block b + 1's
 //      pass 3; stores at the end of their own block made the loop latch's copies of the
 //      prefetched rows wait for them (vmcnt counts the stores issued after the loads).
+// OUT (pfb_dada_store.hpp): OutCf32, the packed [pol][t] complex float32 series (a.out), or
+// OutDada8 / 16 / 32, a single-channel TFP DADA section (SynthBlockArgs::dout; KEPT only) —
+// store_block converts and stores the samples itself, everything before it is the same code.
 template <int RW, bool SPANS, int DK, class SCHED, bool XW = false, class FIRV = NoFir, bool WFLAT = false,
-          int PRIO = 0, int V = 0>
+          int PRIO = 0, int V = 0, class OUT = OutCf32>
 __device__ __forceinline__ void synth_wave_body(const SynthBlockArgs& a, int pol, int tg, const SCHED& sch) {
   constexpr int W = 16 * RW;
   constexpr bool KEPT = (V & 1) != 0, PP = (V & 2) != 0, DEFER = (V & 4) != 0;
@@ -156,6 +161,7 @@ __device__ __forceinline__ void synth_wave_body(const SynthBlockArgs& a, int pol
   static_assert(!DEFER || (KEPT && !FIRV::kOn), "DEFER: KEPT stores of stored stage-1 rows");
   static_assert(!FIRV::kOn || !XW, "the FIR synthesis uses the in-wave pass-1 mapping");
   static_assert(!FIRV::kOn || FIRV::rows(0) <= kTilesB / 160, "FIR tile exceeds the phase tiles");
+  static_assert(!OUT::kDada || (KEPT && !DEFER && !FIRV::kOn), "DADA store: KEPT stores of stored stage-1 rows");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -317,7 +323,11 @@ __device__ __forceinline__ void synth_wave_body(const SynthBlockArgs& a, int pol
   vm_drain();  // (no store wait at the loop head)
 
   // [[maybe_unused]]: the KEPT full-block store offset of the lane (fixed for the kernel)
-  [[maybe_unused]] const int kept_lane = (t1a < RW) ? (t1a * N + t0g + col2) * 8 : (int)0x80000000;
+  // (out_sb: bytes from one output sample of the polarisation to the next — a DADA section
+  // interleaves the P polarisations sample by sample)
+  int out_sb = 8;
+  if constexpr (OUT::kDada) out_sb = a.n_pol * OUT::kBytes;
+  [[maybe_unused]] const int kept_lane = (t1a < RW) ? (t1a * N + t0g + col2) * out_sb : (int)0x80000000;
   constexpr int TL = KEPT ? 3 : 0, TH = KEPT ? 13 : 16;  // pass-3 registers stored
   // block b's outputs: y[t - TL] = pass-3 register t of the lane
   auto store_block = [&](int b, const float2* y) {
@@ -325,6 +335,42 @@ __device__ __forceinline__ void synth_wave_body(const SynthBlockArgs& a, int pol
     const int64_t avail = a.out_limit - ob;
     const int64_t nk = (tmask(a.timing_mask) & 2)
                            ? 0 : max((int64_t)0, avail < a.Lkeep ? avail : (int64_t)a.Lkeep);
+    if constexpr (OUT::kDada) {
+      // Sample ob + i of this polarisation is the complex sample at byte (ob P + pol) kBytes +
+      // i P kBytes of the section: the cf32 offsets below with 8 replaced by sb = P kBytes, from
+      // a descriptor that starts at the workgroup's own first sample and ends with the last
+      // byte of its last one, ((nk - 1) P + 1) kBytes — so neither a byte past sample
+      // out_limit - 1 nor a byte of another polarisation (they lie between this one's samples,
+      // where no offset i sb + [0, kBytes) points) can be written.  As below, the range check
+      // sees the lane offset only, so whatever must be dropped stays in the lane offset.  The
+      // launcher admits L P kBytes = 16 RW N sb <= kRsrcMaxBytes < 2^31 (P kBytes up to 16 for
+      // two polarisations at NBIT 32; more polarisations only with a smaller L): every offset
+      // formed here has a magnitude below (16 RW N) sb, so it neither overflows nor, when
+      // negative (t1 < t1_lo), wraps to less than 2^31 — above every range, as the 0x80000000
+      // of the lanes t1a >= RW is; the positive ones past nk samples fail the check itself.
+      const uint32_t sb = (uint32_t)out_sb;
+      const __amdgpu_buffer_rsrc_t o =
+          make_rsrc(static_cast<char*>(a.dout) + (ob * a.n_pol + pol) * OUT::kBytes,
+                    nk > 0 ? (uint32_t)(((nk - 1) * a.n_pol + 1) * OUT::kBytes) : 0u);
+      const float os = a.dout_scale;
+      // (os * y: a float32 product of its own, then to_sample — pfb_dada_pack's scaled form)
+      if (nk == a.Lkeep) {  // uniform: a whole block, every kept output in range
+        static_for<TL, TH>([&](auto t) {
+          const float2 yv = y[t - TL];
+          OUT::template store<kAuxSynDadaOut>(o, (uint32_t)kept_lane, os * yv.x, os * yv.y,
+                                              (uint32_t)((decltype(t)::value - TL) * RW * N) * sb);
+        });
+      } else {
+        uint32_t base = (t1a < RW) ? (uint32_t)(t1a * N - a.Lov + t0g + col2) * sb : 0x80000000u;
+        asm volatile("" : "+v"(base));  // (the ragged last block only: no hoisted offsets)
+        static_for<TL, TH>([&](auto t) {
+          const float2 yv = y[t - TL];
+          OUT::template store<kAuxSynDadaOut>(o, base + (uint32_t)(decltype(t)::value * RW * N) * sb, os * yv.x,
+                                              os * yv.y);
+        });
+      }
+      return;
+    }
     const __amdgpu_buffer_rsrc_t o = make_rsrc(opol + ob, (uint32_t)nk * 8u);
     if (KEPT && nk == a.Lkeep) {  // uniform: a whole block, every kept output in range
       // output (t1a + RW t1b) N + t0 - L_ov = lane offset + (t1b - 3) RW N (scalar, >= 0)
@@ -508,6 +554,23 @@ void synth_wave_kernel(SynthBlockArgs a) {
   const int b_end = (int)((int64_t)a.n_blocks * (rr + 1) / Rg);
   synth_wave_body<RW, SPANS, DK, RangeSched, XW, FIRV, WFLAT, PRIO, V>(a, blockIdx.y, lt % groups,
                                                                  RangeSched{b_begin, b_end - b_begin});
+}
+
+// The production form of synth_wave_kernel (stored stage-1 rows, XW, kept-register stores,
+// PRIO 1) storing its output as a DADA section (OUT: OutDada8 / 16 / 32; SynthBlockArgs::dout),
+// under a name of its own: the same workgroup -> (phase group, block range) map.
+template <int RW, bool SPANS, bool WFLAT, class OUT>
+__global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(3)))
+void synth_wave_dadaout_kernel(SynthBlockArgs a) {
+  static_assert(OUT::kDada, "the DADA store");
+  const int groups = a.N / kCols;
+  const int lt = a.linear ? (int)blockIdx.x : xcd_tile(blockIdx.x, gridDim.x);
+  const int rr = lt / groups;
+  const int Rg = gridDim.x / groups;
+  const int b_begin = (int)((int64_t)a.n_blocks * rr / Rg);
+  const int b_end = (int)((int64_t)a.n_blocks * (rr + 1) / Rg);
+  synth_wave_body<RW, SPANS, 10, RangeSched, true, NoFir, WFLAT, 1, 1, OUT>(a, blockIdx.y, lt % groups,
+                                                                       RangeSched{b_begin, b_end - b_begin});
 }
 
 }  // namespace pfb

@@ -557,6 +557,89 @@ class SynthesisPlan:
                 byref(n_out), stream))
         return out[:, :n_out.value]
 
+    def _alloc_section(self, like, n: int, out_nbit: int):
+        """-> (device tensor (n, 1, n_pol, 2) of the DADA sample type, its bytes)."""
+        t = _torch()
+        types = {8: t.int8, 16: t.int16, 32: t.float32, 64: t.float64}
+        if int(out_nbit) not in types:
+            # (the C ABI rejects the format; a byte tensor stands in)
+            return t.empty((0, 1, self.n_pol, 2), dtype=t.int8, device=like.device), 0
+        sec = t.empty((max(n, 0), 1, self.n_pol, 2), dtype=types[int(out_nbit)], device=like.device)
+        return sec, sec.numel() * sec.element_size()
+
+    def execute_to_dada(self, chan, out_nbit: int, scale: float = 1.0, sample_offset: int = 1,
+                        stateful: bool = False, layout: str = "pfc"):
+        """The synthesis of device rows ``chan`` written as a single-channel DADA data
+        section: bit for bit ``layout.dada_pack(float32(scale) * execute(chan, ...), out_nbit)``
+        — TFP order, NDIM 2 — without the complex float32 series crossing HBM where the
+        synthesis kernel can store the samples itself (pfb_synthesis_execute_to_dada /
+        pfb_inverse_filterbank_execute_to_dada; ``last_dada_output()`` tells).  Returns a
+        device tensor of shape (n_out, 1, n_pol, 2), int8 / int16 / float32 / float64."""
+        if not is_device_array(chan):
+            raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "execute_to_dada: expects a device tensor")
+        ptc, _ = self._prep_in(chan, layout)
+        if ptc.shape[0] != self.n_pol or ptc.shape[2] != self.n_chan:
+            raise ValueError(f"plan built for (n_pol={self.n_pol}, n_chan={self.n_chan}), "
+                             f"got {tuple(ptc.shape)} [pol, time, chan]")
+        n_dat = ptc.shape[1]
+        if stateful:
+            cap = self.output_length(self.buffered_samples + n_dat)
+        else:
+            cap = self.output_length(max(n_dat - (int(sample_offset) - 1), 0))
+        sec, nbytes = self._alloc_section(ptc, cap, out_nbit)
+        src, dst, stream = c_void_p(ptc.data_ptr()), c_void_p(sec.data_ptr()), _stream_of(ptc, self)
+        n_out = c_int64(0)
+        if stateful:
+            _lib.check(self._lib.pfb_inverse_filterbank_execute_to_dada(
+                self._h, src, n_dat * self.n_chan, n_dat, dst, int(out_nbit), float(scale), nbytes,
+                byref(n_out), stream))
+        else:
+            _lib.check(self._lib.pfb_synthesis_execute_to_dada(
+                self._h, src, n_dat * self.n_chan, n_dat, int(sample_offset), dst, int(out_nbit),
+                float(scale), nbytes, byref(n_out), stream))
+        return sec[:n_out.value]
+
+    def execute_dada_to_dada(self, raw, nbit: int, out_nbit: int, scale: float = 1.0, ndim: int = 2,
+                             lowcbf: bool = False, sample_offset: int = 1, stateful: bool = False):
+        """``execute_dada`` written as a DADA data section like ``execute_to_dada``: file
+        bytes in, file bytes out (pfb_synthesis_execute_dada_to_dada /
+        pfb_inverse_filterbank_execute_dada_to_dada); ``last_dada_input()`` and
+        ``last_dada_output()`` tell which sides the kernels read and wrote in place."""
+        if not is_device_array(raw):
+            raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "execute_dada_to_dada: expects a device tensor")
+        raw = raw.contiguous()
+        if int(nbit) not in (8, 16, 32, 64) or int(ndim) not in (1, 2):
+            n_dat = 0  # (the C ABI rejects the format)
+        else:
+            per = self.n_chan * self.n_pol * int(ndim) * (int(nbit) // 8)
+            n_dat = (raw.numel() * raw.element_size()) // per
+            if lowcbf:
+                n_dat -= n_dat % 32
+        if stateful:
+            cap = self.output_length(self.buffered_samples + n_dat)
+        else:
+            cap = self.output_length(max(n_dat - (int(sample_offset) - 1), 0))
+        sec, nbytes = self._alloc_section(raw, cap, out_nbit)
+        order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
+        src, dst, stream = c_void_p(raw.data_ptr()), c_void_p(sec.data_ptr()), _stream_of(raw, self)
+        n_out = c_int64(0)
+        if stateful:
+            _lib.check(self._lib.pfb_inverse_filterbank_execute_dada_to_dada(
+                self._h, src, int(nbit), int(ndim), order, n_dat, dst, int(out_nbit), float(scale), nbytes,
+                byref(n_out), stream))
+        else:
+            _lib.check(self._lib.pfb_synthesis_execute_dada_to_dada(
+                self._h, src, int(nbit), int(ndim), order, n_dat, int(sample_offset), dst, int(out_nbit),
+                float(scale), nbytes, byref(n_out), stream))
+        return sec[:n_out.value]
+
+    def last_dada_output(self) -> str:
+        """How the plan's last to-DADA call wrote its section: 'fused' (the synthesis kernel
+        stored the file's own bytes), 'staged' (the cf32 series packed by a second launch),
+        'none' (no such call, or a cf32-output call since) — pfb_synthesis_last_dada_output."""
+        m = int(self._lib.pfb_synthesis_last_dada_output(self._h))
+        return {_lib.PFB_DADA_OUTPUT_FUSED: "fused", _lib.PFB_DADA_OUTPUT_STAGED: "staged"}.get(m, "none")
+
     def execute_view(self, x, sample_offset: int = 1, stateful: bool = False, out=None):
         """The synthesis of a strided view: ``x`` is any complex64 device tensor view shaped
         (n_pol, n_dat, n_chan); its strides and storage offset go to the C ABI as they are

@@ -277,6 +277,52 @@ class InverseFilterBank(DeChannelizer):
         out = plan.execute_dada(raw, nbit, ndim=ndim, lowcbf=lowcbf, stateful=True)
         return self, out[:, None, :]
 
+    def _quantised_output(self) -> bool:
+        # (InverseFilterBank.m has no output quantiser; an object given FilterBank's
+        # rndOutput / rmsOutput hooks packs what ``execute`` returns, as FilterBank does: a
+        # quantiser needs the variance of the whole output)
+        return bool(getattr(self, "rndOutput", False) or getattr(self, "rmsOutput", 0.0))
+
+    @staticmethod
+    def _pack_out(out, nbit, scale):
+        """The (n_pol, 1, n_out) series ``execute`` returns -> the scaled, packed section."""
+        import torch
+        buf = out[:, 0, :].contiguous()[:, :, None]  # (n_pol, n_out, 1 channel)
+        if float(scale) != 1.0:
+            # (per component, in float32: not a complex product)
+            buf = torch.view_as_complex(torch.view_as_real(buf) * float(scale))
+        return layout.dada_pack(buf, nbit).reshape(buf.shape[1], 1, buf.shape[0], 2)
+
+    def execute_to_dada(self, input, nbit: int, scale: float = 1.0):  # noqa: A002
+        """``execute`` of the next chunk (device rows) written as a single-channel DADA data
+        section: returns ``(self, section)`` with ``section`` the (n_out, 1, n_pol, 2) device
+        tensor of int8 / int16 / float32 / float64 samples (TFP order), bit for bit
+        ``layout.dada_pack(float32(scale) * out, nbit)`` of ``execute``'s output, and the same
+        carry (``SynthesisPlan.execute_to_dada``)."""
+        if self._quantised_output():
+            _, out = self.execute(input)
+            return self, self._pack_out(out, nbit, scale)
+        shape = tuple(input.shape)
+        if int(self.sample_offset) < 0:
+            raise ValueError("sample_offset is 0-based (>= 0)")
+        plan = self._ensure_plan(shape[0], shape[1])
+        plan.set_stream_sample_offset(int(self.sample_offset))
+        return self, plan.execute_to_dada(input, nbit, scale=scale, stateful=True)
+
+    def execute_dada_to_dada(self, raw, in_nbit: int, out_nbit: int, scale: float = 1.0, ndim: int = 2,
+                             lowcbf: bool = False, n_pol: int = 1):
+        """``execute_dada`` written as a DADA data section like ``execute_to_dada``: file
+        bytes in, file bytes out (``SynthesisPlan.execute_dada_to_dada``)."""
+        if self._quantised_output():
+            _, out = self.execute_dada(raw, in_nbit, ndim=ndim, lowcbf=lowcbf, n_pol=n_pol)
+            return self, self._pack_out(out, out_nbit, scale)
+        if int(self.sample_offset) < 0:
+            raise ValueError("sample_offset is 0-based (>= 0)")
+        plan = self._ensure_plan(int(n_pol), int(self.nchan))
+        plan.set_stream_sample_offset(int(self.sample_offset))
+        return self, plan.execute_dada_to_dada(raw, in_nbit, out_nbit, scale=scale, ndim=ndim, lowcbf=lowcbf,
+                                               stateful=True)
+
     def reset(self):
         if self._plan is not None:
             self._plan.reset()

@@ -119,12 +119,13 @@ def synthesize(input_data_file_path, input_fft_length: int = None, input_overlap
     tsamp = float(hdr.get("TSAMP", "1"))
     sh["TSAMP"] = _num2str(tsamp / (os_factor.de / os_factor.nu) / channels)
     # polyphase_synthesis(data, 1, nf, os_factor, deripple, 1, ov, taper) of the file's
-    # samples, read by the synthesis from the section's own bytes (no unpacked copy)
+    # samples, read by the synthesis from the section's own bytes (no unpacked copy) and
+    # written as the output file's NBIT 32 section (no cf32 series packed afterwards)
     plan = synthesis_plan(channels, os_factor, nf, ov, True, 1, bool(deripple), taps, taper, None,
                           int(hdr["NPOL"]), raw.device.index or 0)
-    out = plan.execute_dada(raw, int(hdr["NBIT"]), ndim=int(hdr["NDIM"]))[:, None, :]
+    section = plan.execute_dada_to_dada(raw, int(hdr["NBIT"]), 32, ndim=int(hdr["NDIM"]))
     path = os.path.join(output_dir, output_file_name)
-    dada.write_dada_file(path, out, sh)
+    dada.write_dada_section_file(path, section, sh)
     return dada.DADAFile(path, device).load_data()
 
 
