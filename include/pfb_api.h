@@ -520,6 +520,77 @@ pfb_status pfb_inverse_filterbank_execute_dada_to_dada(pfb_synthesis_plan* plan,
                                                        int64_t* n_out, void* stream);
 int32_t pfb_synthesis_last_dada_output(const pfb_synthesis_plan* plan);
 
+/* The round trip from file bytes to file bytes (DADARead.m:58-83, then the analysis ->
+ * synthesis sequence of test_data_pipeline.m:114,132, each step followed by
+ * write_dada_data.m:32-50): pfb_roundtrip_execute and its two halves with a single-channel DADA
+ * section in, the channelised file's section and the output file's section out.  Device memory
+ * only.  `in` is the section pfb_analysis_execute_dada reads: n_dat samples x 1 channel x the
+ * plans' n_pol x ndim values of nbit (8/16/32/64), in `order`; in TFP order complex sample t of
+ * polarisation p is element t * n_pol + p.  `chan` is the channelised section as the pipeline
+ * saves it: TFP, NDIM 2, NBIT 32 float, no scale — element (row k, channel c, polarisation p),
+ * with N the channel count and P = n_pol, at byte ((k * N + c) * P + p) * 8, re then im; for
+ * one polarisation these are the bytes of pfb_roundtrip_execute's cf32 `chan`.  It is float on
+ * purpose: the reference's synthesis reads the channelised file, and the stage-1 rows are taken
+ * before the store, so only an unquantised product makes the fused call compute what the
+ * two-file pipeline computes.  `out` is the section pfb_synthesis_execute_to_dada writes:
+ * sample t of polarisation p at byte (t * P + p) * 2 * out_nbit / 8, out_nbit 8/16/32/64, each
+ * component to_sample(out_scale * y).
+ * The bytes written, *n_chan_rows, *n_out and the status codes are those of this sequence, bit
+ * for bit, on every path: pfb_dada_unpack of `in` into a packed [pol][t] buffer;
+ * pfb_roundtrip_execute on it; pfb_dada_pack(..., 32) of its `chan`; both components of its
+ * `out` multiplied by out_scale in float32; pfb_dada_pack at out_nbit with n_chan = 1.  Exactly
+ * rows [0, *n_chan_rows) of `chan` and samples [0, *n_out) of `out` are written and not one
+ * byte beyond.  pfb_roundtrip_analysis_execute_dada and pfb_roundtrip_synthesis_execute_to_dada
+ * are the two halves (see pfb_roundtrip_analysis_execute): together they equal the whole call
+ * bit for bit, and the synthesis half works after either analysis half, cf32 or DADA — the
+ * stage-1 rows and the plan's key are the same; it is refused with PFB_ERR_INVALID_ARG exactly
+ * where pfb_roundtrip_synthesis_execute is.  PFB_ERR_UNSUPPORTED as for the cf32 calls: a
+ * PFB_ANALYSIS_LOWCBF plan, and the halves on a plan pair that takes the chunked pipeline.
+ * Every check runs before any launch or state change.  PFB_ERR_INVALID_ARG: null plans, null
+ * buffers when samples are given or output is due, nbit or out_nbit not 8/16/32/64, ndim not
+ * 1/2, an unknown order (LowCBF: n_dat a multiple of 32), `in` not aligned to one value of
+ * nbit, `chan` not 4-byte aligned, `out` not aligned to one value of out_nbit, a non-finite
+ * out_scale, sample_offset < 1, and the plan-mismatch conditions of pfb_roundtrip_execute.
+ * PFB_ERR_BUFFER_TOO_SMALL, with nothing written and *n_chan_rows and *n_out set as the cf32
+ * call sets them: chan_capacity_bytes below K * N * P * 8, out_capacity_bytes below
+ * n_out * P * 2 * out_nbit / 8.
+ * FUSED: one analysis launch (analysis_stream_rt_dada_kernel) loads the section's bytes, stores
+ * the float product section and emits the stage-1 rows; the Nf = 256 wave synthesis then stores
+ * the output section.  No unpacked series, no cf32 series and no pack launch exist.  All of:
+ * nbit 8, 16 or 32, NDIM 2, TFP order, `in` aligned to one complex sample; `chan` aligned to 8
+ * bytes; out_nbit 8, 16 or 32 and `out` aligned to one complex sample; a plan pair whose cf32
+ * round trip takes the fused path through the streaming analysis and the wave kernel on 2-row
+ * runs (PFB_ANALYSIS_BUNTON, n_chan 256, os 8/7 or 4/3, 12 or 13 tap phases; input_fft_length
+ * 256, input_overlap 48; no combine permutation, temporal-taper gain or spectral taper; no
+ * chunk size set; (sample_offset - 1) a multiple of 16); sections within the descriptor limits
+ * of pfb_analysis_execute_dada and pfb_analysis_execute_to_dada.  A half needs its own side's
+ * conditions only.  The stage-1 rows are STORED in these calls whatever
+ * pfb_synthesis_set_stage1_rows says (no recomputing kernel reads a section);
+ * pfb_synthesis_last_stage1_rows reports it.
+ * STAGED: everything else (padded or n_chan > 256 pairs, other offsets, NBIT 64, NDIM 1, LowCBF
+ * order, a `chan` or `out` aligned to a value only, a call too short for one synthesis block)
+ * runs the sequence above inside the call on plan-owned staging buffers, so these calls accept
+ * every plan pair pfb_roundtrip_execute accepts, the chunked pipeline included; with one
+ * polarisation and an 8-byte aligned `chan` the cf32 round trip writes straight into `chan`.
+ * pfb_analysis_last_dada_input reports the path of the input, pfb_analysis_last_dada_output
+ * that of the product section and pfb_synthesis_last_dada_output that of the output section
+ * (unchanged by a call without rows); FUSED is all three FUSED.  (Measured A/B against the
+ * sequence: DESIGN.md §4.9.) */
+pfb_status pfb_roundtrip_execute_dada_to_dada(pfb_analysis_plan* analysis, pfb_synthesis_plan* synthesis,
+                                              const void* in, int32_t nbit, int32_t ndim, int32_t order,
+                                              int64_t n_dat, void* chan, int64_t chan_capacity_bytes,
+                                              int64_t* n_chan_rows, int64_t sample_offset, void* out,
+                                              int32_t out_nbit, float out_scale, int64_t out_capacity_bytes,
+                                              int64_t* n_out, void* stream);
+pfb_status pfb_roundtrip_analysis_execute_dada(pfb_analysis_plan* analysis, pfb_synthesis_plan* synthesis,
+                                               const void* in, int32_t nbit, int32_t ndim, int32_t order,
+                                               int64_t n_dat, void* chan, int64_t chan_capacity_bytes,
+                                               int64_t* n_chan_rows, int64_t sample_offset, void* stream);
+pfb_status pfb_roundtrip_synthesis_execute_to_dada(pfb_analysis_plan* analysis, pfb_synthesis_plan* synthesis,
+                                                   int64_t n_dat, int64_t sample_offset, void* out,
+                                                   int32_t out_nbit, float out_scale,
+                                                   int64_t out_capacity_bytes, int64_t* n_out, void* stream);
+
 /* The synthesis calls reading their channelised rows strided (device memory only): channel c
  * of row t of polarisation p is in[p * in_pol_stride + t * in_row_stride + c * in_chan_stride]
  * — the input-side mirror of pfb_filterbank_execute_strided.  Polarisations may interleave

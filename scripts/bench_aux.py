@@ -17,6 +17,10 @@ one MI355X, as algorithmic HBM bytes / time against the 8 TB/s peak.
   * --only-dada-synthesis-output: synthesis into a DADA section at the C2 shape, the pair
     (pfb_synthesis_execute[_dada], scale, pfb_dada_pack) against pfb_synthesis_execute_to_dada /
     pfb_synthesis_execute_dada_to_dada, interleaved, and the cf32 synthesis alone
+  * --only-dada-roundtrip: the round trip from a single-channel DADA section into the
+    channelised and the output sections at the C2 unit, the sequence (pfb_dada_unpack,
+    pfb_roundtrip_execute, packs) against pfb_roundtrip_execute_dada_to_dada, interleaved, and
+    the two halves pipelined over two streams
   * --only-twostage-inverse: TwoStageInverseFilterBank with the channel gather against the
     strided input (pfb_inverse_filterbank_execute_strided), interleaved
 
@@ -68,6 +72,8 @@ def main():
                     help="the dada_output A/B alone (--reps: calls per timed window)")
     ap.add_argument("--only-dada-synthesis-output", action="store_true",
                     help="the dada_synthesis_output A/B alone (--reps: calls per timed window)")
+    ap.add_argument("--only-dada-roundtrip", action="store_true",
+                    help="the dada_roundtrip A/B alone (--reps: calls per timed window)")
     ap.add_argument("--only-twostage-inverse", action="store_true",
                     help="the inverse cascade's gather vs strided-input A/B alone (--reps: calls per window)")
     ap.add_argument("--rounds", type=int, default=15,
@@ -110,6 +116,8 @@ def main():
         return dada_output(torch, pfb, dev, max(args.reps, 20), args.rounds)
     if args.only_dada_synthesis_output:
         return dada_synthesis_output(torch, pfb, dev, max(args.reps, 20), args.rounds)
+    if args.only_dada_roundtrip:
+        return dada_roundtrip(torch, pfb, dev, max(args.reps, 20), args.rounds)
     if args.only_twostage_inverse:
         return twostage_inverse(torch, pfb, noise, max(args.reps, 20), max(args.rounds, 5))
     # ---- C2' (4/3) round trip
@@ -580,6 +588,245 @@ def dada_synthesis_output(torch, pfb, dev, reps, rounds):
             del src
         del plan, cf, scaled
         torch.cuda.empty_cache()
+
+
+def dada_roundtrip(torch, pfb, dev, reps, rounds):
+    """Single-channel DADA section -> the channelised file's float section and the output file's
+    section, the C2 unit (2^24 samples, 256 ch, 8/7, 3073 taps, Nf 256, Ov 48, tukey, deripple).
+    A: the sequence a caller had before — pfb_dada_unpack, pfb_roundtrip_execute, pfb_dada_pack at
+    NBIT 32 of the product when there are two polarisations (one polarisation's cf32 product is
+    the section already), both components of the output times the scale in float32 (one
+    elementwise pass), pfb_dada_pack with one channel.  B: pfb_roundtrip_execute_dada_to_dada.
+    Both through the C ABI into preallocated buffers.  The sections are asserted equal first;
+    then `rounds` windows of `reps` calls of each side, alternating A and B in one process,
+    after a warm-up of both.  One line per cell with the median, min, max and quartiles of each
+    side's per-call time.  stays_fused: B's median lies below A's by more than the larger of the
+    two sides' min-to-max spreads.  The last line is the pipelined row: the two halves over two
+    streams on two plan pairs, the steps captured as one graph as bench.py captures its headline
+    (A: unpack + cf32 analysis half on one stream, cf32 synthesis half + packs on the other; B:
+    the two DADA halves), in windows of replays."""
+    from ctypes import byref, c_int64, c_void_p
+    from ska_pst_dsp_model_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator(device=dev).manual_seed(8)
+    N, n = 256, 1 << 24
+    taps = pfb.design_PFB_FIR_filter(N, "8/7", 12)
+    win = pfb.PFBWindow().lookup["tukey"](256, 48)
+    dts = {8: torch.int8, 16: torch.int16, 32: torch.float32}
+    TFP = _lib.PFB_DADA_TFP
+
+    def plans(n_pol):
+        return (pfb.AnalysisPlan(taps, N, "8/7", "polyphase_analysis", n_pol),
+                pfb.SynthesisPlan(N, "8/7", 256, 48, True, 1, True, taps, win, None, n_pol))
+
+    def section(nbit, n_pol):
+        if nbit == 32:
+            return torch.randn((n * n_pol * 2,), device=dev, generator=g)
+        lim = 1 << (nbit - 1)
+        return torch.randint(-lim, lim, (n * n_pol * 2,), dtype=dts[nbit], device=dev, generator=g)
+
+    def stats(t):
+        q = np.percentile(t, [0, 25, 50, 75, 100])
+        return {k: round(float(v), 4) for k, v in zip(("min", "q25", "median", "q75", "max"), q)}
+
+    def ptr(t):
+        return c_void_p(t.data_ptr())
+
+    def cur():
+        return c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    class Unit:
+        """One plan pair with the buffers of both sides."""
+
+        def __init__(self, n_pol, in_nbit, nbit, src):
+            self.n_pol, self.in_nbit, self.nbit, self.src = n_pol, in_nbit, nbit, src
+            self.ana, self.syn = plans(n_pol)
+            self.K = self.ana.output_length(n)
+            self.n_o = self.syn.output_length(self.K)
+            self.x = torch.empty((n_pol, n), dtype=torch.complex64, device=dev)
+            self.chan = torch.empty((n_pol, self.K, N), dtype=torch.complex64, device=dev)
+            self.cf = torch.empty((n_pol, self.n_o), dtype=torch.complex64, device=dev)
+            self.scaled = torch.empty_like(self.cf)
+            # (one polarisation: the cf32 product is the float section)
+            self.chan_a = torch.empty((self.K, N, n_pol, 2), device=dev) if n_pol > 1 else torch.view_as_real(
+                self.chan[0])[:, :, None, :]
+            self.chan_b = torch.empty((self.K, N, n_pol, 2), device=dev)
+            self.sec_a = torch.empty((self.n_o, 1, n_pol, 2), dtype=dts[nbit], device=dev)
+            self.sec_b = torch.empty_like(self.sec_a)
+            self.kr, self.no = c_int64(0), c_int64(0)
+            self.scale = 1.0
+
+        def a_analysis(self, whole):
+            _lib.check(lib.pfb_dada_unpack(ptr(self.src), self.in_nbit, 2, TFP, n, 1, self.n_pol, ptr(self.x), n, cur()))
+            if whole:
+                _lib.check(lib.pfb_roundtrip_execute(self.ana._h, self.syn._h, ptr(self.x), n, n, ptr(self.chan),
+                                                     self.K * N, self.K, byref(self.kr), 1, ptr(self.cf), self.n_o,
+                                                     self.n_o, byref(self.no), cur()))
+            else:
+                _lib.check(lib.pfb_roundtrip_analysis_execute(self.ana._h, self.syn._h, ptr(self.x), n, n,
+                                                              ptr(self.chan), self.K * N, self.K, byref(self.kr), 1,
+                                                              cur()))
+
+        def a_output(self, whole):
+            if not whole:
+                _lib.check(lib.pfb_roundtrip_synthesis_execute(self.ana._h, self.syn._h, n, 1, ptr(self.cf), self.n_o,
+                                                               self.n_o, byref(self.no), cur()))
+            if self.n_pol > 1:
+                _lib.check(lib.pfb_dada_pack(ptr(self.chan), self.K * N, self.K, N, self.n_pol, ptr(self.chan_a), 32,
+                                             cur()))
+            torch.mul(torch.view_as_real(self.cf), self.scale, out=torch.view_as_real(self.scaled))
+            _lib.check(lib.pfb_dada_pack(ptr(self.scaled), self.n_o, self.n_o, 1, self.n_pol, ptr(self.sec_a),
+                                         self.nbit, cur()))
+
+        def side_a(self):
+            self.a_analysis(True)
+            self.a_output(True)
+
+        def side_b(self):
+            _lib.check(lib.pfb_roundtrip_execute_dada_to_dada(
+                self.ana._h, self.syn._h, ptr(self.src), self.in_nbit, 2, TFP, n, ptr(self.chan_b),
+                self.chan_b.numel() * 4, byref(self.kr), 1, ptr(self.sec_b), self.nbit, self.scale,
+                self.sec_b.numel() * self.sec_b.element_size(), byref(self.no), cur()))
+
+        def b_analysis(self):
+            _lib.check(lib.pfb_roundtrip_analysis_execute_dada(
+                self.ana._h, self.syn._h, ptr(self.src), self.in_nbit, 2, TFP, n, ptr(self.chan_b),
+                self.chan_b.numel() * 4, byref(self.kr), 1, cur()))
+
+        def b_output(self):
+            _lib.check(lib.pfb_roundtrip_synthesis_execute_to_dada(
+                self.ana._h, self.syn._h, n, 1, ptr(self.sec_b), self.nbit, self.scale,
+                self.sec_b.numel() * self.sec_b.element_size(), byref(self.no), cur()))
+
+        def set_scale(self):
+            # the output's component rms at a third of the integer range (0.37 for NBIT 32)
+            self.side_a()
+            rms = float(torch.view_as_real(self.cf).square().mean().sqrt())
+            self.scale = float(np.float32((((1 << (self.nbit - 1)) - 1) / 3.0 if self.nbit != 32 else 0.37) / rms))
+
+        def check(self, what):
+            self.sec_a.zero_()
+            self.sec_b.zero_()
+            self.chan_b.zero_()
+            self.side_a()
+            self.side_b()
+            paths = (self.ana.last_dada_input(), self.ana.last_dada_output(), self.syn.last_dada_output())
+            torch.cuda.synchronize()
+            assert (self.kr.value, self.no.value) == (self.K, self.n_o), what
+            assert torch.equal(self.sec_a, self.sec_b), f"{what}: output sections differ"
+            assert torch.equal(self.chan_a, self.chan_b), f"{what}: product sections differ"
+            return paths
+
+        def bytes(self, fused):
+            P, K, n_o = self.n_pol, self.K, self.n_o
+            e_in, e_out = 2 * self.in_nbit // 8, 2 * self.nbit // 8
+            # A: the section read, the series written and read, the product written (and, two
+            # polarisations, read and rewritten), the output written, read, rewritten scaled,
+            # read again and the section written.  B fused: section read, product and section
+            # written.  (The stage-1 rows, written and read once on both sides, are left out.)
+            a = P * (n * (e_in + 16) + K * N * (8 + (16 if P > 1 else 0)) + n_o * (32 + e_out))
+            b = P * (n * e_in + K * N * 8 + n_o * e_out)
+            return int(a), int(b if fused else a)
+
+    for n_pol in (1, 2):
+        for in_nbit, nbit in ((16, 16), (8, 8), (16, 32), (32, 32)):
+            what = f"dada_roundtrip {in_nbit}->{nbit} {n_pol} pol"
+            u = Unit(n_pol, in_nbit, nbit, section(in_nbit, n_pol))
+            u.set_scale()
+            paths = u.check(what)
+            fused = paths == ("fused", "fused", "fused")
+            for _ in range(2):
+                timeit(torch, u.side_a, reps)
+                timeit(torch, u.side_b, reps)
+            ta, tb = [], []
+            for _ in range(rounds):
+                ta.append(timeit(torch, u.side_a, reps))
+                tb.append(timeit(torch, u.side_b, reps))
+            a, b = stats(ta), stats(tb)
+            spread = max(a["max"] - a["min"], b["max"] - b["min"])
+            ab, bb = u.bytes(fused)
+            print(json.dumps({
+                "kernel": "dada_roundtrip", "shape": "C2 2^24 256ch 8/7 Nf256 Ov48 tukey deripple", "n_pol": n_pol,
+                "in_nbit": in_nbit, "out_nbit": nbit, "rows": u.K, "n_out": u.n_o, "paths": list(paths),
+                "calls_per_window": reps, "windows": rounds, "sections_equal": True,
+                "A_unpack_roundtrip_packs_ms": a, "B_roundtrip_dada_to_dada_ms": b,
+                "A_spread_ms": round(a["max"] - a["min"], 4), "B_spread_ms": round(b["max"] - b["min"], 4),
+                "B_below_A_by_ms": round(a["median"] - b["median"], 4),
+                "B_over_A": round(b["median"] / a["median"], 4),
+                "stays_fused": bool(fused and a["median"] - b["median"] > spread),
+                "A_bytes": ab, "B_bytes": bb}), flush=True)
+            del u
+            torch.cuda.empty_cache()
+
+    # ---- the pipelined row: two plan pairs, two streams, the steps of a window as one graph
+    n_pol, in_nbit, nbit, steps = 1, 16, 16, 8
+    units = [Unit(n_pol, in_nbit, nbit, section(in_nbit, n_pol)) for _ in range(2)]
+    for u in units:
+        u.set_scale()
+        u.check("dada_roundtrip pipelined")
+    D = len(units)
+
+    def capture(ana_half, out_half):
+        def enqueue():
+            sa = torch.cuda.current_stream(dev)
+            ss = torch.cuda.Stream(device=dev)
+            ss.wait_stream(sa)
+            ev_a = [torch.cuda.Event() for _ in range(steps)]
+            ev_s = [torch.cuda.Event() for _ in range(steps)]
+            for i in range(steps):
+                u = units[i % D]
+                if i >= D:
+                    sa.wait_event(ev_s[i - D])
+                ana_half(u)
+                ev_a[i].record(sa)
+                ss.wait_event(ev_a[i])
+                with torch.cuda.stream(ss):
+                    out_half(u)
+                ev_s[i].record(ss)
+            sa.wait_stream(ss)
+        cs = torch.cuda.Stream(device=dev)
+        cs.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(cs):
+            enqueue()                                     # warm-up: every buffer the halves need exists
+        torch.cuda.current_stream(dev).wait_stream(cs)
+        torch.cuda.synchronize(dev)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            enqueue()
+        torch.cuda.synchronize(dev)
+        return graph.replay
+
+    pipe_a = capture(lambda u: u.a_analysis(False), lambda u: u.a_output(False))
+    pipe_b = capture(lambda u: u.b_analysis(), lambda u: u.b_output())
+    for u in units:
+        u.sec_a.zero_()
+        u.sec_b.zero_()
+        u.chan_b.zero_()
+    pipe_a()
+    pipe_b()
+    torch.cuda.synchronize()
+    for u in units:
+        assert torch.equal(u.sec_a, u.sec_b) and torch.equal(u.chan_a, u.chan_b), "pipelined: sections differ"
+    paths = (units[0].ana.last_dada_input(), units[0].ana.last_dada_output(), units[0].syn.last_dada_output())
+    w = max(1, reps // steps)
+    for _ in range(2):
+        timeit(torch, pipe_a, w)
+        timeit(torch, pipe_b, w)
+    ta, tb = [], []
+    for _ in range(rounds):
+        ta.append(timeit(torch, pipe_a, w) / steps)
+        tb.append(timeit(torch, pipe_b, w) / steps)
+    a, b = stats(ta), stats(tb)
+    spread = max(a["max"] - a["min"], b["max"] - b["min"])
+    ab, bb = units[0].bytes(paths == ("fused", "fused", "fused"))
+    print(json.dumps({
+        "kernel": "dada_roundtrip_pipelined", "shape": "C2 2^24 256ch 8/7 Nf256 Ov48 tukey deripple",
+        "n_pol": n_pol, "in_nbit": in_nbit, "out_nbit": nbit, "plan_pairs": D, "streams": 2,
+        "steps_per_graph": steps, "replays_per_window": w, "windows": rounds, "paths": list(paths),
+        "sections_equal": True, "A_ms_per_step": a, "B_ms_per_step": b,
+        "A_spread_ms": round(a["max"] - a["min"], 4), "B_spread_ms": round(b["max"] - b["min"], 4),
+        "B_below_A_by_ms": round(a["median"] - b["median"], 4), "B_over_A": round(b["median"] / a["median"], 4),
+        "meets_rule": bool(a["median"] - b["median"] > spread), "A_bytes": ab, "B_bytes": bb}), flush=True)
 
 
 def twostage_inverse(torch, pfb, noise, reps, rounds):

@@ -1,6 +1,8 @@
 // pfb_ana_stream.hpp — the streaming Bunton analysis for N = 256 (polyphase_analysis.m:83-121),
 // analysis_stream_kernel (instantiated in pfb_analysis.hip).
 #pragma once
+#include <type_traits>
+
 #include "pfb_common.hpp"
 #include "pfb_dada_store.hpp"
 #include "pfb_sample.hpp"
@@ -168,11 +170,15 @@ struct SinkStore {
 // inside it are wave barriers (round 6; timing variants r06_v14: the FFT was 30 of the
 // kernel's 78 us with four workgroup barriers a step, memory traffic masked or not)
 // IN: the input fetch (InCf32, or a DADA section read in place)
-// OUT: the product's store (OutCf32, or a DADA section written in place: ZOUT 0, GS 0)
+// OUT: the product's store (OutCf32, or a DADA section written in place: ZOUT 0, GS 0 — and the
+// file-to-file round trip's one combination, a section read in place, the NBIT 32 float product
+// section and the 2-row runs: ZOUT 2, IN a DADA class, OutDada32)
 template <int N, int P, int NU, int DE, int ZOUT, bool LCBF, int GS, int TV = 0, class IN = InCf32,
           class OUT = OutCf32>
 __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int pol, int w, int nw) {
-  static_assert(!OUT::kDada || (ZOUT == 0 && GS == 0 && TV == 0), "the DADA store: the plain product only");
+  static_assert(!OUT::kDada || (GS == 0 && TV == 0 &&
+                                (ZOUT == 0 || (ZOUT == 2 && !LCBF && IN::kDada && std::is_same<OUT, OutDada32>::value))),
+                "the DADA store: the plain product, or the round trip's float section with 2-row runs");
   using SH = StreamShape<N, P, NU, DE>;
   constexpr int M = SH::M, PE = SH::PE, QS = SH::QS, T = SH::T, NEW = SH::NEW, WIN = SH::WIN;
   constexpr bool kWR = (TV & 8) == 0 && wave_rows_ok<N, T, NT>();
@@ -436,6 +442,17 @@ template <int N, int P, int NU, int DE, bool LCBF, class IN, class OUT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void analysis_stream_dadaout_kernel(AnalysisArgs a) {
   const int w = a.linear ? (int)blockIdx.x : xcd_tile(blockIdx.x, gridDim.x);
   analysis_stream_body<N, P, NU, DE, 0, LCBF, 0, 0, IN, OUT>(a, blockIdx.y, w, gridDim.x);
+}
+
+// The round trip's kernel (ZOUT 2: the stage-1 rows in 2-row runs, stored as ever) reading a
+// DADA section in place and storing its product as the NBIT 32 float section of the channelised
+// file (AnalysisArgs::din, dout with dout_scale 1: 1.0f * x keeps every bit of x, so the section
+// holds the cf32 kernel's product) — pfb_roundtrip_execute_dada_to_dada.  A kernel of its own
+// name again (pfb_ana_stream_rtdada.hip instantiates them).
+template <int N, int P, int NU, int DE, class IN>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void analysis_stream_rt_dada_kernel(AnalysisArgs a) {
+  const int w = a.linear ? (int)blockIdx.x : xcd_tile(blockIdx.x, gridDim.x);
+  analysis_stream_body<N, P, NU, DE, 2, false, 0, 0, IN, OutDada32>(a, blockIdx.y, w, gridDim.x);
 }
 
 // Workgroups per polarisation of a streaming launch, each a contiguous range of steps

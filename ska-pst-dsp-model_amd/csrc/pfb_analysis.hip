@@ -914,6 +914,9 @@ hipError_t launch_analysis(const AnalysisArgs& a, hipStream_t s) {
     const bool generic_ok = !fused && a.zblk == 2 && a.z_row0 == 0 && fir_window_applies(a);
     if (!stream_ok && !generic_ok) return hipErrorInvalidValue;
   }
+  // (the file-to-file round trip: section in, float section and 2-row runs out — a launcher of
+  // its own, with its own checks; every other launch keeps din and dout apart from z, below)
+  if (a.din && a.dout && a.z) return launch_stream_rt_dada(a, s);
   if (a.din && (!analysis_reads_dada(a, a.din_nbit) || a.z)) return hipErrorInvalidValue;
   // (a DADA product: the streaming kernel's plain product only)
   if (a.dout && (!analysis_writes_dada(a, a.dout_nbit) || a.z || a.out_rs != 0)) return hipErrorInvalidValue;

@@ -300,7 +300,10 @@ static pfb_status analysis_run(pfb_analysis_plan* p, const float2* in, int64_t i
   if (K_end <= row0) return PFB_OK;
   if (dd) p->last_dada = PFB_DADA_INPUT_FUSED;
   if (od) {
-    if (z || lay || row0 != 0) return fail(PFB_ERR_UNSUPPORTED, "DADA output: the plain product only");
+    // (with stage-1 rows: only the file-to-file round trip's launch — a section read in place,
+    // the float section and 2-row runs, pfb::launch_stream_rt_dada)
+    const bool rt = z && dd && od->nbit == 32 && zblk == 2 && z_stage == 0 && !pre && !co;
+    if ((z && !rt) || lay || row0 != 0) return fail(PFB_ERR_UNSUPPORTED, "DADA output: the plain product only");
     out = nullptr;
     out_ps = 0;
   }
@@ -2333,6 +2336,25 @@ pfb_status pfb_inverse_filterbank_reset(pfb_synthesis_plan* p) {
 // the same inputs as pfb_analysis_execute + pfb_synthesis_execute, so both results are
 // bit-identical to the separate calls (the fused path below: see its comment).
 
+// What the file-to-file calls (roundtrip_dada, below) ask of roundtrip_run; the cf32 calls pass
+// none of it.
+struct RtOpt {
+  // FUSED: the analysis launch reads the section dd in place and stores the product as the
+  // float section od (`in` and `chan` then only have to pass the checks); the synthesis stores
+  // through the plan's dout, which the caller sets.  Only for a call that `wave2` named.
+  const AnaDada* dd = nullptr;
+  const AnaOut* od = nullptr;
+  // the stage-1 rows are stored whatever pfb_synthesis_set_stage1_rows says (no recomputing
+  // kernel reads a section, and a plan-owned staging buffer is no input to come back to)
+  bool stored = false;
+  // every check of the call and the allocation of the rows, then return: no launch, no change
+  // of the split round trip's key
+  bool dry = false;
+  // (dry) set when the call takes the fused path through the streaming analysis and the
+  // Nf = 256 wave kernel on stored 2-row runs
+  bool* wave2 = nullptr;
+};
+
 // phase 0: the whole round trip; 1 / 2: only the analysis / only the synthesis half of the
 // fused path (pfb_roundtrip_analysis_execute / pfb_roundtrip_synthesis_execute), which hand
 // the stage-1 rows over in the synthesis plan's scratch
@@ -2340,7 +2362,8 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
                                 int64_t in_ps, int64_t n_dat, pfb_cf32* chan, int64_t chan_ps,
                                 int64_t chan_cap, int64_t* n_chan_rows, int64_t sample_offset,
                                 pfb_cf32* out, int64_t out_ps, int64_t out_cap, int64_t* n_out,
-                                void* stream, int phase) {
+                                void* stream, int phase, const RtOpt& opt = RtOpt{}) {
+  if (opt.wave2) *opt.wave2 = false;
   if (!pa || !ps || (!in && n_dat > 0 && phase != 2)) return fail(PFB_ERR_INVALID_ARG, "null argument");
   if (pa->device != ps->device) return fail(PFB_ERR_INVALID_ARG, "plans on different devices");
   if (pa->variant == pfb::kLowCbf)
@@ -2374,7 +2397,7 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
   }
   const float2* x = (const float2*)in;
   float2* y = (float2*)chan;
-  if (B == 0) return phase == 2 ? PFB_OK : analysis_run(pa, x, in_ps, n_dat, y, chan_ps, 0, K, K, s);
+  if (B == 0) return (phase == 2 || opt.dry) ? PFB_OK : analysis_run(pa, x, in_ps, n_dat, y, chan_ps, 0, K, K, s);
 
   // Fused: the analysis kernel also writes the synthesis stage-1 rows (the channel IFFT
   // of every row it produces, taken as N^2 x its FIR sums before the FFT rather than from
@@ -2415,7 +2438,8 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
   // series — the same FIR sums, bit for bit (555 instead of 727 MB of HBM traffic per C2
   // step).  Where the wave kernel takes the run layout (zblk) and has a FIR variant
   // (pfb_synthesis_set_stage1_rows).
-  const bool synth_fir_on = ps->stage1 == PFB_STAGE1_RECOMPUTED || (ps->stage1 == PFB_STAGE1_AUTO && kSynthFirDefault);
+  const bool synth_fir_on =
+      !opt.stored && (ps->stage1 == PFB_STAGE1_RECOMPUTED || (ps->stage1 == PFB_STAGE1_AUTO && kSynthFirDefault));
   FirSrc fsrc{(const float2*)in, in_ps, n_dat, off / std::max(pa->nu, 1), pa->gtab.as<float>(), pa->nu, pa->de,
               pa->P + 1};
   bool fir = false;
@@ -2437,8 +2461,10 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
                     "n_dat %lld and sample_offset %lld (run pfb_roundtrip_analysis_execute with the same "
                     "arguments first)",
                     (long long)n_dat, (long long)sample_offset);
+      if (opt.dry) return PFB_OK;
       return synthesis_blocks(ps, nullptr, 0, 0, B, (float2*)out, out_ps, olen, s, 0, &fsrc);
     }
+    if (opt.dry) return PFB_OK;
     zkey_clear(ps);
     pfb_status st = analysis_run(pa, x, in_ps, n_dat, y, chan_ps, 0, K, K, s);
     if (st != PFB_OK) return st;
@@ -2465,6 +2491,9 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
   } else if (fuse) {
     // the rows of the whole call stay resident; a device without room for them takes the
     // chunked pipeline below (its scratch is one chunk's rows) instead of failing
+    // (a dry run returns before the key is cleared below: rows that a key vouches for go with
+    // the buffer this allocation replaces)
+    if (opt.dry && (!ps->Z.p || ps->Z.bytes < zbytes)) zkey_clear(ps);
     const hipError_t ze = ps->Z.ensure(zbytes);
     if (ze == hipErrorOutOfMemory) {
       (void)hipGetLastError();
@@ -2473,15 +2502,22 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
       return fail(PFB_ERR_HIP, "round trip stage-1 rows (%zu bytes): %s", zbytes, hipGetErrorString(ze));
     }
   }
+  // (the file-to-file calls: FUSED is this path only, and is asked for only where a dry run
+  // of the same call named it)
+  const bool wave2 = fuse && pa->fused && zblk == 2;
+  if ((opt.dd || opt.od) && !(wave2 && opt.dd && opt.od))
+    return fail(PFB_ERR_UNSUPPORTED, "round trip: these plans have no kernel that reads and stores sections");
   if (phase != 0) {
     // the split round trip exists for the fused path only (one scratch of rows handed over)
     if (!fuse) return fail(PFB_ERR_UNSUPPORTED, "split round trip: these plans take the chunked pipeline "
                                                 "(use pfb_roundtrip_execute)");
+    if (opt.wave2) *opt.wave2 = wave2;
+    if (opt.dry) return PFB_OK;
     float2* Z = ps->Z.as<float2>();
     if (phase == 1) {
       zkey_clear(ps);
       pfb_status st = analysis_run(pa, x, in_ps, n_dat, y, chan_ps, 0, K, K, s, Z, zrows * pa->N, z0, 0, nullptr,
-                                   zblk);
+                                   zblk, nullptr, 0, nullptr, opt.dd, opt.od);
       if (st != PFB_OK) return st;
       ps->zkey_plan = pa->serial;
       std::copy(zkey, zkey + 5, ps->zkey);
@@ -2489,6 +2525,8 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
     }
     return synthesis_blocks(ps, Z + (off - z0) * pa->N, zrows * pa->N, 0, B, (float2*)out, out_ps, olen, s, zblk);
   }
+  if (opt.wave2) *opt.wave2 = wave2;
+  if (opt.dry) return PFB_OK;
   zkey_clear(ps);  // phase 0 reuses Z
   if (fuse) {
     float2* Z = ps->Z.as<float2>();
@@ -2505,7 +2543,8 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
         st = analysis_run(pa, x, in_ps, n_dat, y, chan_ps, 0, K, K, s, Z, zrows * pa->N, z0, 0, nullptr, zblk,
                           nullptr, 2);
     } else {
-      st = analysis_run(pa, x, in_ps, n_dat, y, chan_ps, 0, K, K, s, Z, zrows * pa->N, z0, 0, nullptr, zblk);
+      st = analysis_run(pa, x, in_ps, n_dat, y, chan_ps, 0, K, K, s, Z, zrows * pa->N, z0, 0, nullptr, zblk, nullptr,
+                        0, nullptr, opt.dd, opt.od);
     }
     if (st != PFB_OK) return st;
     return synthesis_blocks(ps, Z + (off - z0) * pa->N, zrows * pa->N, 0, B, (float2*)out, out_ps,
@@ -2570,6 +2609,189 @@ pfb_status pfb_roundtrip_synthesis_execute(pfb_analysis_plan* pa, pfb_synthesis_
                                            int64_t out_cap, int64_t* n_out, void* stream) {
   return roundtrip_run(pa, ps, nullptr, n_dat, n_dat, nullptr, 0, 0, nullptr, sample_offset, out, out_ps,
                        out_cap, n_out, stream, 2);
+}
+
+// ---- the round trip from a DADA section into DADA sections (pfb_api.h)
+// The sections of a file-to-file call.  Each cell of the A/B (DESIGN.md §4.9,
+// profiles/dada_roundtrip_ab.jsonl) that met the decision rule stays FUSED; one that did not
+// is listed in rt_dada_cell_staged and takes the STAGED sequence.
+struct RtSections {
+  AnaSection in;            // phase != 2
+  void* chan;               // phase != 2: the float product section
+  int64_t chan_cap_bytes;
+  void* out;                // phase != 1
+  int32_t out_nbit;
+  float out_scale;
+  int64_t out_cap_bytes;
+};
+
+// (polarisations, input NBIT, output NBIT) cells the A/B sent STAGED: none was measured slower
+static bool rt_dada_cell_staged(int /*n_pol*/, int /*in_nbit*/, int /*out_nbit*/) { return false; }
+
+// FUSED, input side: the round trip's kernel loads such a section itself
+static bool roundtrip_dada_in_fusable(const pfb_analysis_plan* p, const AnaSection& sec, const void* chan) {
+  if (sec.ndim != 2 || sec.order != PFB_DADA_TFP || (sec.nbit != 8 && sec.nbit != 16 && sec.nbit != 32)) return false;
+  if (reinterpret_cast<uintptr_t>(sec.base) % (size_t)(sec.nbit / 4) != 0) return false;
+  if (reinterpret_cast<uintptr_t>(chan) % 8 != 0) return false;
+  pfb::AnalysisArgs a{};
+  a.variant = p->variant;
+  a.N = p->N;
+  a.M = p->M;
+  a.P = p->P;
+  a.nu = p->nu;
+  a.n_pol = p->n_pol;
+  return pfb::stream_rt_dada_supported(a, sec.nbit);
+}
+
+// phase: roundtrip_run's.  Every check — roundtrip_run's own among them, through its dry run —
+// comes before the first launch and before the split round trip's key changes; then FUSED (the
+// analysis launch reads and stores the sections, the wave synthesis stores the output section)
+// or STAGED (unpack, the cf32 round trip on plan-owned buffers, the packs).
+static pfb_status roundtrip_dada(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, const RtSections& sec, int64_t n_dat,
+                                 int64_t* n_chan_rows, int64_t sample_offset, int64_t* n_out, void* stream,
+                                 int phase) {
+  if (!pa || !ps) return fail(PFB_ERR_INVALID_ARG, "null plan");
+  if (phase != 2) {
+    const pfb_status st = ana_section_check(pa, sec.in, n_dat);
+    if (st != PFB_OK) return st;
+    if (reinterpret_cast<uintptr_t>(sec.in.base) % (size_t)(sec.in.nbit / 8) != 0)
+      return fail(PFB_ERR_INVALID_ARG, "input section not aligned to its NBIT");
+    if (reinterpret_cast<uintptr_t>(sec.chan) % 4 != 0)
+      return fail(PFB_ERR_INVALID_ARG, "channelised section not aligned to a float");
+  }
+  if (phase != 1) {
+    if (sec.out_nbit != 8 && sec.out_nbit != 16 && sec.out_nbit != 32 && sec.out_nbit != 64)
+      return fail(PFB_ERR_INVALID_ARG, "output NBIT must be 8, 16, 32 or 64");
+    if (!std::isfinite(sec.out_scale)) return fail(PFB_ERR_INVALID_ARG, "output scale is not finite");
+    if (reinterpret_cast<uintptr_t>(sec.out) % (size_t)(sec.out_nbit / 8) != 0)
+      return fail(PFB_ERR_INVALID_ARG, "output section not aligned to its NBIT");
+  }
+  // the cf32 call's checks, in its order, with the capacities in its units: whole rows of the
+  // product section, whole samples (all polarisations) of the output section
+  const int64_t big = INT64_MAX / 4;  // (a stride that passes: nothing is launched)
+  const int64_t chan_cap = phase != 2 ? std::max<int64_t>(sec.chan_cap_bytes, 0) / ((int64_t)pa->N * pa->n_pol * 8) : 0;
+  const int64_t out_cap =
+      phase != 1 ? std::max<int64_t>(sec.out_cap_bytes, 0) / ((int64_t)ps->n_pol * 2 * (sec.out_nbit / 8)) : 0;
+  const pfb_cf32* in_c = static_cast<const pfb_cf32*>(sec.in.base);
+  pfb_cf32* chan_c = static_cast<pfb_cf32*>(sec.chan);
+  pfb_cf32* out_c = static_cast<pfb_cf32*>(sec.out);
+  int64_t K = 0, olen = 0;
+  bool wave2 = false;
+  RtOpt dry;
+  dry.stored = true;
+  dry.dry = true;
+  dry.wave2 = &wave2;
+  pfb_status st = phase == 2 ? roundtrip_run(pa, ps, nullptr, n_dat, n_dat, nullptr, 0, 0, &K, sample_offset, out_c,
+                                             big, out_cap, &olen, stream, 2, dry)
+                             : roundtrip_run(pa, ps, in_c, big, n_dat, chan_c, big, chan_cap, &K, sample_offset,
+                                             out_c, big, phase == 1 ? 0 : out_cap, &olen, stream, phase, dry);
+  if (n_chan_rows && phase != 2) *n_chan_rows = K;
+  if (n_out && phase != 1) *n_out = olen;
+  if (st != PFB_OK || K == 0) return st;
+  if (phase == 2 && olen == 0) return PFB_OK;
+
+  hipStream_t s = (hipStream_t)stream;
+  const int P = pa->n_pol;
+  const bool in_fused = phase != 2 && roundtrip_dada_in_fusable(pa, sec.in, sec.chan);
+  const bool out_fused = phase != 1 && synthesis_dada_out_fusable(ps, sec.out, sec.out_nbit);
+  const bool cell = phase == 0 && rt_dada_cell_staged(P, sec.in.nbit, sec.out_nbit);
+  const bool fused = wave2 && !cell && (phase == 2 || in_fused) && (phase == 1 || out_fused);
+  RtOpt run;
+  run.stored = true;
+  if (fused) {
+    // (the sections stand in for the cf32 buffers in the callee's checks; the launches go
+    // through dd / od and the synthesis plan's dout only)
+    const AnaDada dd{sec.in.base, sec.in.nbit};
+    const AnaOut od{sec.chan, 32, 1.0f};
+    if (phase != 2) {
+      run.dd = &dd;
+      run.od = &od;
+    }
+    if (phase != 1) {
+      ps->dout = sec.out;
+      ps->dout_nbit = sec.out_nbit;
+      ps->dout_scale = sec.out_scale;
+    }
+    st = phase == 2 ? roundtrip_run(pa, ps, nullptr, n_dat, n_dat, nullptr, 0, 0, nullptr, sample_offset, out_c, olen,
+                                    olen, nullptr, stream, 2, run)
+                    : roundtrip_run(pa, ps, in_c, n_dat, n_dat, chan_c, K * pa->N, K, nullptr, sample_offset, out_c,
+                                    olen, olen, nullptr, stream, phase, run);
+    ps->dout = nullptr;
+    if (st != PFB_OK) return st;
+    if (phase != 2) pa->last_dada_out = PFB_DADA_OUTPUT_FUSED;  // (last_dada: analysis_run, FUSED)
+    if (phase != 1) ps->last_dada_out = PFB_DADA_OUTPUT_FUSED;
+    return PFB_OK;
+  }
+
+  // STAGED: pfb_dada_unpack, the cf32 call, pfb_dada_pack at NBIT 32 of the product, the scaled
+  // pack of the output.  One polarisation's float section is the cf32 product itself.
+  float2* x = nullptr;
+  float2* y = nullptr;
+  float2* o = nullptr;
+  bool chan_direct = false;
+  if (phase != 2) {
+    HIPCHK(pa->stage_in.ensure((size_t)P * n_dat * sizeof(float2)));
+    x = pa->stage_in.as<float2>();
+    chan_direct = P == 1 && reinterpret_cast<uintptr_t>(sec.chan) % 8 == 0;
+    if (chan_direct) {
+      y = static_cast<float2*>(sec.chan);
+    } else {
+      HIPCHK(pa->dada_stage.ensure((size_t)P * K * pa->N * sizeof(float2)));
+      y = pa->dada_stage.as<float2>();
+    }
+  }
+  if (phase != 1 && olen > 0) {
+    HIPCHK(ps->stage_out.ensure((size_t)P * olen * sizeof(float2)));
+    o = ps->stage_out.as<float2>();
+  }
+  if (phase != 2) {
+    st = ana_section_unpack(pa, sec.in, 0, n_dat, x, n_dat, s);
+    if (st != PFB_OK) return st;
+  }
+  st = phase == 2 ? roundtrip_run(pa, ps, nullptr, n_dat, n_dat, nullptr, 0, 0, nullptr, sample_offset,
+                                  reinterpret_cast<pfb_cf32*>(o), olen, olen, nullptr, stream, 2, run)
+                  : roundtrip_run(pa, ps, reinterpret_cast<const pfb_cf32*>(x), n_dat, n_dat,
+                                  reinterpret_cast<pfb_cf32*>(y), K * pa->N, K, nullptr, sample_offset,
+                                  reinterpret_cast<pfb_cf32*>(o), olen, olen, nullptr, stream, phase, run);
+  if (st != PFB_OK) return st;
+  if (phase != 2) {
+    if (!chan_direct) {
+      st = pfb_dada_pack(reinterpret_cast<const pfb_cf32*>(y), K * pa->N, K, pa->N, P, sec.chan, 32, stream);
+      if (st != PFB_OK) return st;
+    }
+    pa->last_dada = PFB_DADA_INPUT_STAGED;
+    pa->last_dada_out = PFB_DADA_OUTPUT_STAGED;
+  }
+  if (phase != 1) {
+    if (olen > 0) HIPCHK(pfb::launch_dada_pack_scaled(o, olen, olen, 1, P, sec.out, sec.out_nbit, sec.out_scale, s));
+    ps->last_dada_out = PFB_DADA_OUTPUT_STAGED;
+  }
+  return PFB_OK;
+}
+
+pfb_status pfb_roundtrip_execute_dada_to_dada(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, const void* in,
+                                              int32_t nbit, int32_t ndim, int32_t order, int64_t n_dat, void* chan,
+                                              int64_t chan_cap_bytes, int64_t* n_chan_rows, int64_t sample_offset,
+                                              void* out, int32_t out_nbit, float out_scale, int64_t out_cap_bytes,
+                                              int64_t* n_out, void* stream) {
+  const RtSections sec{AnaSection{in, nbit, ndim, order}, chan, chan_cap_bytes, out, out_nbit, out_scale, out_cap_bytes};
+  return roundtrip_dada(pa, ps, sec, n_dat, n_chan_rows, sample_offset, n_out, stream, 0);
+}
+
+pfb_status pfb_roundtrip_analysis_execute_dada(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, const void* in,
+                                               int32_t nbit, int32_t ndim, int32_t order, int64_t n_dat, void* chan,
+                                               int64_t chan_cap_bytes, int64_t* n_chan_rows, int64_t sample_offset,
+                                               void* stream) {
+  const RtSections sec{AnaSection{in, nbit, ndim, order}, chan, chan_cap_bytes, nullptr, 0, 1.f, 0};
+  return roundtrip_dada(pa, ps, sec, n_dat, n_chan_rows, sample_offset, nullptr, stream, 1);
+}
+
+pfb_status pfb_roundtrip_synthesis_execute_to_dada(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, int64_t n_dat,
+                                                   int64_t sample_offset, void* out, int32_t out_nbit,
+                                                   float out_scale, int64_t out_cap_bytes, int64_t* n_out,
+                                                   void* stream) {
+  const RtSections sec{AnaSection{nullptr, 0, 0, 0}, nullptr, 0, out, out_nbit, out_scale, out_cap_bytes};
+  return roundtrip_dada(pa, ps, sec, n_dat, nullptr, sample_offset, n_out, stream, 2);
 }
 
 // ------------------------------------------------------------------ utilities

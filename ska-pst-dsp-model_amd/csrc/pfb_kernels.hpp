@@ -130,6 +130,13 @@ hipError_t launch_stream_dadaout(const AnalysisArgs& a, bool lcbf, hipStream_t s
 // those kernels read a DADA section of in_nbit in place when they write out_nbit (the same
 // NBIT, or any integer NBIT into NBIT 32); other pairs come in unpacked, as cf32
 bool dadaout_reads_dada(int in_nbit, int out_nbit);
+// The file-to-file round trip's analysis launch (pfb_ana_stream_rtdada.hip): the streaming
+// kernel reading the section `din` (in_nbit 8 / 16 / 32) in place, storing the product as the
+// NBIT 32 float section `dout` (dout_scale 1) and the stage-1 rows z in 2-row runs (zblk 2) —
+// the one launch that takes din or dout together with z.  Bunton, N 256, os 8/7 or 4/3, 12 or 13
+// phases; no carry, no read offset.
+bool stream_rt_dada_supported(const AnalysisArgs& a, int in_nbit);
+hipError_t launch_stream_rt_dada(const AnalysisArgs& a, hipStream_t s);
 // pfb_dada_pack with both components multiplied by `scale` in float32 first (pfb_layout.hip)
 hipError_t launch_dada_pack_scaled(const float2* in, int64_t in_pol_stride, int64_t n_dat, int C, int P,
                                    void* out, int nbit, float scale, hipStream_t s);

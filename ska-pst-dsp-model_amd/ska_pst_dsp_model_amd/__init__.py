@@ -12,6 +12,7 @@ from .config import Rational, default_config, load_config
 from .core import (AnalysisPlan, SynthesisPlan, polyphase_analysis, polyphase_analysis_padded,
                    polyphase_analysis_lowcbf,
                    polyphase_synthesis, roundtrip, roundtrip_analysis, roundtrip_synthesis,
+                   roundtrip_dada, roundtrip_analysis_dada, roundtrip_synthesis_to_dada,
                    calc_output_nbins)
 from .filterbank import (Channelizer, DeChannelizer, FilterBank, InverseFilterBank,
                          TwoStageFilterBank, TwoStageInverseFilterBank)
@@ -28,7 +29,8 @@ __all__ = [
     "Channelizer", "DeChannelizer", "FilterBank", "InverseFilterBank", "TwoStageFilterBank",
     "TwoStageInverseFilterBank", "design_PFB_FIR_filter", "design_PFB_FIR_filter_two_stage",
     "read_fir_filter_coeff", "PFBWindow", "identity_taper", "roundtrip", "roundtrip_analysis",
-    "roundtrip_synthesis", "calc_output_nbins",
+    "roundtrip_synthesis", "roundtrip_dada", "roundtrip_analysis_dada", "roundtrip_synthesis_to_dada",
+    "calc_output_nbins",
     "sgcht", "PureTone", "Impulse", "FrequencyComb", "TestPureTone", "TestImpulse",
     "TestFrequencyComb",
 ]

@@ -158,6 +158,16 @@ SYMBOLS = [
                                                               c_int64, c_void_p, c_int32, c_float, c_int64,
                                                               POINTER(c_int64), c_void_p]),
     ("pfb_synthesis_last_dada_output", c_int32, [c_void_p]),
+    ("pfb_roundtrip_execute_dada_to_dada", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                                     c_int64, c_void_p, c_int64, POINTER(c_int64), c_int64,
+                                                     c_void_p, c_int32, c_float, c_int64, POINTER(c_int64),
+                                                     c_void_p]),
+    ("pfb_roundtrip_analysis_execute_dada", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                                      c_int64, c_void_p, c_int64, POINTER(c_int64), c_int64,
+                                                      c_void_p]),
+    ("pfb_roundtrip_synthesis_execute_to_dada", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                                          c_int32, c_float, c_int64, POINTER(c_int64),
+                                                          c_void_p]),
     ("pfb_synthesis_execute_strided", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
                                                 c_int64, c_int64, c_void_p, c_int64, c_int64,
                                                 POINTER(c_int64), c_void_p]),

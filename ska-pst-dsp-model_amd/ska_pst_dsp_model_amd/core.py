@@ -799,6 +799,125 @@ def roundtrip_synthesis(analysis: AnalysisPlan, synthesis: SynthesisPlan, n_dat:
     return out
 
 
+_SECTION_TYPES = {8: "int8", 16: "int16", 32: "float32", 64: "float64"}
+
+
+def _section_samples(raw, n_pol: int, nbit: int, ndim: int, lowcbf: bool) -> int:
+    """Samples per polarisation a single-channel section tensor holds (0: a format the C ABI
+    rejects)."""
+    if int(nbit) not in (8, 16, 32, 64) or int(ndim) not in (1, 2):
+        return 0
+    n_dat = (raw.numel() * raw.element_size()) // (n_pol * int(ndim) * (int(nbit) // 8))
+    return n_dat - n_dat % 32 if lowcbf else n_dat
+
+
+def _alloc_rt_section(shape, nbit: int, device):
+    """-> (device tensor of the DADA sample type, its bytes); a format the C ABI rejects gets
+    an empty byte tensor to stand in."""
+    t = _torch()
+    if int(nbit) not in _SECTION_TYPES:
+        return t.empty((0,) + tuple(shape[1:]), dtype=t.int8, device=device), 0
+    sec = t.empty(tuple(max(int(v), 0) for v in shape), dtype=getattr(t, _SECTION_TYPES[int(nbit)]),
+                  device=device)
+    return sec, sec.numel() * sec.element_size()
+
+
+def _hold_captured_section(synthesis, raw):
+    """A captured launch holds the section's address for every replay, and ``raw`` may be the
+    temporary ``.contiguous()`` made: keep it alive as long as the plan (roundtrip_synthesis's
+    rule for captured inputs; one entry per address)."""
+    if _torch().cuda.is_current_stream_capturing():
+        synthesis.__dict__.setdefault("_graph_inputs", {})[raw.data_ptr()] = raw
+
+
+def roundtrip_dada(analysis: AnalysisPlan, synthesis: SynthesisPlan, raw, nbit: int, out_nbit: int,
+                   scale: float = 1.0, sample_offset: int = 1, ndim: int = 2, lowcbf: bool = False):
+    """The round trip from file bytes to file bytes (``pfb_roundtrip_execute_dada_to_dada``):
+    ``raw`` is a device tensor holding a single-channel DADA data section ([t][pol][re, im],
+    ``nbit`` 8/16/32/64).  Returns ``(chan_section, out_section)``: the channelised file's
+    section, float32 of shape (K, n_chan, n_pol, 2), and the output file's section of shape
+    (n_out, 1, n_pol, 2), int8 / int16 / float32 / float64, each component
+    ``to_sample(float32(scale) * y)``.  Bit for bit ``layout.dada_unpack`` -> ``roundtrip`` ->
+    ``layout.dada_pack`` of both results; ``analysis.last_dada_input()``,
+    ``analysis.last_dada_output()`` and ``synthesis.last_dada_output()`` tell whether the
+    kernels read and wrote the sections themselves."""
+    if not is_device_array(raw):
+        raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "roundtrip_dada: expects a device tensor")
+    if analysis.n_pol != synthesis.n_pol:
+        raise ValueError(f"plans built for n_pol={analysis.n_pol}/{synthesis.n_pol}")
+    raw = raw.contiguous()
+    n_pol = analysis.n_pol
+    n_dat = _section_samples(raw, n_pol, nbit, ndim, lowcbf)
+    K = analysis.output_length(n_dat)
+    n_out = synthesis.output_length(max(K - (int(sample_offset) - 1), 0))
+    chan, chan_bytes = _alloc_rt_section((K, analysis.n_chan, n_pol, 2), 32, raw.device)
+    out, out_bytes = _alloc_rt_section((n_out, 1, n_pol, 2), out_nbit, raw.device)
+    order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
+    kr, no = c_int64(0), c_int64(0)
+    _lib.check(_lib.load().pfb_roundtrip_execute_dada_to_dada(
+        analysis._h, synthesis._h, c_void_p(raw.data_ptr()), int(nbit), int(ndim), order, n_dat,
+        c_void_p(chan.data_ptr()), chan_bytes, byref(kr), int(sample_offset),
+        c_void_p(out.data_ptr()), int(out_nbit), float(scale), out_bytes, byref(no),
+        _stream_of(raw, analysis, synthesis)))
+    _hold_captured_section(synthesis, raw)
+    return chan[:kr.value], out[:no.value]
+
+
+def roundtrip_analysis_dada(analysis: AnalysisPlan, synthesis: SynthesisPlan, raw, nbit: int,
+                            sample_offset: int = 1, ndim: int = 2, lowcbf: bool = False):
+    """The analysis half of ``roundtrip_dada`` (``pfb_roundtrip_analysis_execute_dada``):
+    returns the channelised section and leaves the stage-1 rows in ``synthesis``'s scratch
+    for ``roundtrip_synthesis_to_dada`` (or ``roundtrip_synthesis``).  The rows are always
+    stored, so the synthesis half never comes back to ``raw``.  ``PfbError`` (unsupported)
+    when the plans take the chunked pipeline."""
+    if not is_device_array(raw):
+        raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "roundtrip_analysis_dada: expects a device tensor")
+    if analysis.n_pol != synthesis.n_pol:
+        raise ValueError(f"plans built for n_pol={analysis.n_pol}/{synthesis.n_pol}")
+    raw = raw.contiguous()
+    n_pol = analysis.n_pol
+    n_dat = _section_samples(raw, n_pol, nbit, ndim, lowcbf)
+    K = analysis.output_length(n_dat)
+    chan, chan_bytes = _alloc_rt_section((K, analysis.n_chan, n_pol, 2), 32, raw.device)
+    order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
+    kr = c_int64(0)
+    _lib.check(_lib.load().pfb_roundtrip_analysis_execute_dada(
+        analysis._h, synthesis._h, c_void_p(raw.data_ptr()), int(nbit), int(ndim), order, n_dat,
+        c_void_p(chan.data_ptr()), chan_bytes, byref(kr), int(sample_offset),
+        _stream_of(raw, analysis, synthesis)))
+    _hold_captured_section(synthesis, raw)
+    return chan[:kr.value]
+
+
+def roundtrip_synthesis_to_dada(analysis: AnalysisPlan, synthesis: SynthesisPlan, n_dat: int,
+                                out_nbit: int, scale: float = 1.0, sample_offset: int = 1, device=None):
+    """The synthesis half (``pfb_roundtrip_synthesis_execute_to_dada``) of a
+    ``roundtrip_analysis_dada`` or ``roundtrip_analysis`` call with the same ``n_dat`` /
+    ``sample_offset``: returns the output section, equal to ``roundtrip_dada``'s bit for bit.
+    Runs on the current stream of ``device`` (default: the synthesis plan's)."""
+    t = _torch()
+    n_pol = synthesis.n_pol
+    K = analysis.output_length(int(n_dat))
+    n_out = synthesis.output_length(max(K - (int(sample_offset) - 1), 0))
+    dv = t.device("cuda", synthesis.device if device is None else device)
+    out, out_bytes = _alloc_rt_section((n_out, 1, n_pol, 2), out_nbit, dv)
+    no = c_int64(0)
+    stream = _stream_of(out, analysis, synthesis)
+    _lib.check(_lib.load().pfb_roundtrip_synthesis_execute_to_dada(
+        analysis._h, synthesis._h, int(n_dat), int(sample_offset), c_void_p(out.data_ptr()),
+        int(out_nbit), float(scale), out_bytes, byref(no), stream))
+    xin = getattr(synthesis, "_rt_input", None)
+    if xin is not None:
+        # (roundtrip_synthesis's rule for the input of a cf32 analysis half with recomputed rows)
+        if not t.cuda.is_current_stream_capturing():
+            xin.record_stream(t.cuda.current_stream(out.device))
+        else:
+            held = synthesis.__dict__.setdefault("_graph_inputs", {})
+            held[xin.data_ptr()] = xin
+        synthesis._rt_input = None
+    return out[:no.value]
+
+
 # ============================================================================ helpers
 def calc_output_nbins(nbins, channels, os_factor, filter_taps, input_fft_length, input_overlap):
     """calc_output_nbins.m:1-28 (same arguments: ``os_factor`` a Rational / "nu/de" / Matlab
