@@ -972,7 +972,7 @@ hipError_t launch_analysis(const AnalysisArgs& a, hipStream_t s) {
     RowFftArgs rz{a.z + a.row0 * a.N, a.z_pol_stride, a.out + a.row0 * a.N, a.out_pol_stride, rows, a.zrev,
                   nullptr, a.twN, 1.0f / (float)a.N, 0, 0, 0, a.K_total};
     rz.in_run = a.zblk == 2 ? 1 : 0;
-    rz.rev = a.zrev != nullptr ? 1 : 0;  // (zrev is always the index reversal, pfb_api.hip)
+    rz.rev = a.zrev != nullptr ? 1 : 0;  // (zrev is always the index reversal, analysis_host_tables)
     if (a.variant == kBunton) return dispatch_row_fft<-1>(a.N, rz, a.n_pol, s);
     return dispatch_row_fft<+1>(a.N, rz, a.n_pol, s);
   }

@@ -246,7 +246,7 @@ struct StridedRowStore {
     const uint32_t off = ok ? (uint32_t)((row * rs + j * cs) * 8) : 0xFFFFFFF0u;
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, cscale(v, scale)), r, off, 0, kAuxStrided);
   }
-  // the host checks that (T rs + jn cs) * 8 fits one descriptor (pfb_api.hip)
+  // the host checks that (T rs + jn cs) * 8 fits one descriptor (pfb_filterbank_execute_strided)
   __device__ __forceinline__ static StridedRowStore rows(float2* base, int64_t k0, int T, int64_t k_lo,
                                                           int64_t k_hi, int rs, int cs, int split,
                                                           int shift, int nsel, int N, float scale) {

@@ -27,23 +27,11 @@
 #include <vector>
 
 #include "pfb_api.h"
+#include "pfb_host.hpp"
 #include "pfb_kernels.hpp"
 #include "pfb_sample.hpp"
 
-pfb_status pfb_set_error(pfb_status s, const char* msg);  // pfb_api.hip
-
 namespace {
-
-#define LCHK(expr)                                                                          \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      char m_[512];                                                                         \
-      snprintf(m_, sizeof(m_), "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__,   \
-               __LINE__);                                                                   \
-      return pfb_set_error(e_ == hipErrorOutOfMemory ? PFB_ERR_OOM : PFB_ERR_HIP, m_);     \
-    }                                                                                       \
-  } while (0)
 
 pfb_status bad(const char* msg) { return pfb_set_error(PFB_ERR_INVALID_ARG, msg); }
 
@@ -441,10 +429,10 @@ pfb_status pfb_dada_unpack(const void* in, int32_t nbit, int32_t ndim, int32_t o
   const bool lc = order == PFB_DADA_LOWCBF;
   float2* o = (float2*)out;
   switch (nbit) {
-    case 8: LCHK((launch_unpack<int8_t>(in, ndim, lc, n_dat, n_chan, n_pol, o, out_pol_stride, s))); break;
-    case 16: LCHK((launch_unpack<int16_t>(in, ndim, lc, n_dat, n_chan, n_pol, o, out_pol_stride, s))); break;
-    case 32: LCHK((launch_unpack<float>(in, ndim, lc, n_dat, n_chan, n_pol, o, out_pol_stride, s))); break;
-    case 64: LCHK((launch_unpack<double>(in, ndim, lc, n_dat, n_chan, n_pol, o, out_pol_stride, s))); break;
+    case 8: HIPCHK((launch_unpack<int8_t>(in, ndim, lc, n_dat, n_chan, n_pol, o, out_pol_stride, s))); break;
+    case 16: HIPCHK((launch_unpack<int16_t>(in, ndim, lc, n_dat, n_chan, n_pol, o, out_pol_stride, s))); break;
+    case 32: HIPCHK((launch_unpack<float>(in, ndim, lc, n_dat, n_chan, n_pol, o, out_pol_stride, s))); break;
+    case 64: HIPCHK((launch_unpack<double>(in, ndim, lc, n_dat, n_chan, n_pol, o, out_pol_stride, s))); break;
     default: return bad("pfb_dada_unpack: NBIT must be 8, 16, 32 or 64");
   }
   return PFB_OK;
@@ -466,7 +454,7 @@ pfb_status pfb_dada_pack(const pfb_cf32* in, int64_t in_pol_stride, int64_t n_da
     case 64: hipLaunchKernelGGL(dada_pack_kernel<double>, g, TPB, 0, s, src, in_pol_stride, n_dat, n_chan, n_pol, (double*)out); break;
     default: return bad("pfb_dada_pack: NBIT must be 8, 16, 32 or 64");
   }
-  LCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return PFB_OK;
 }
 
@@ -487,7 +475,7 @@ pfb_status pfb_gather_channels(const pfb_cf32* in, int64_t in_outer_stride, int6
   hipLaunchKernelGGL(gather_kernel, grid, TPB, 0, s, (const float2*)in, in_outer_stride,
                      in_row_stride, (float2*)out, out_outer_stride, out_row_stride, n_rows, n_sel,
                      src0, split, shift);
-  LCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return PFB_OK;
 }
 
@@ -502,7 +490,7 @@ pfb_status pfb_corner_turn(const pfb_cf32* in, int64_t in_outer_stride, int64_t 
   hipLaunchKernelGGL(transpose_kernel, grid, TPB, 0, (hipStream_t)stream, (const float2*)in,
                      in_outer_stride, in_row_stride, n_rows, n_cols, (float2*)out, out_outer_stride,
                      out_row_stride);
-  LCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return PFB_OK;
 }
 
@@ -517,23 +505,23 @@ pfb_status pfb_quantize(const pfb_cf32* in, int64_t in_pol_stride, int64_t n, in
   if (rms > 0 && n * (int64_t)n_pol < 2) return bad("pfb_quantize: var() of a single sample");
   hipStream_t s = (hipStream_t)stream;
   double* st = nullptr;
-  LCHK(stats_buffer(&st));
+  HIPCHK(stats_buffer(&st));
   if (n_pol > 65535) return bad("pfb_quantize: n_pol > 65535");
   const dim3 g(std::max(1u, grid_stride_blocks(n * n_pol) / (unsigned)n_pol), (unsigned)n_pol);
   if (rms > 0) {
-    LCHK(hipMemsetAsync(st, 0, 3 * sizeof(double), s));
+    HIPCHK(hipMemsetAsync(st, 0, 3 * sizeof(double), s));
     // few workgroups (each ends in three double atomics on one cache line, which serialise
     // in L2): ~4 per CU in total, every thread streaming many 16-byte loads
     const dim3 gm(std::max(1u, std::min(g.x, 1024u / (unsigned)n_pol)), (unsigned)n_pol);
     hipLaunchKernelGGL(moments_kernel, gm, TPB, 0, s, (const float2*)in, in_pol_stride, n, n_pol, st);
-    LCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   hipLaunchKernelGGL(quantize_kernel, g, TPB, 0, s, (const float2*)in, in_pol_stride, (float2*)out,
                      out_pol_stride, n, n_pol, rms, st);
-  LCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   if (scale) {
-    LCHK(hipMemcpyAsync(scale, st + 3, sizeof(double), hipMemcpyDeviceToHost, s));
-    LCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpyAsync(scale, st + 3, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
   }
   return PFB_OK;
 }
@@ -548,7 +536,7 @@ pfb_status pfb_device_copy(void* dst, const void* src, int64_t n_bytes, void* st
   const dim3 g((unsigned)blocks);
   hipLaunchKernelGGL(copy_kernel, g, TPB, 0, (hipStream_t)stream, (const copy_v4f*)src,
                      (copy_v4f*)dst, n4);
-  LCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return PFB_OK;
 }
 

@@ -1,7 +1,7 @@
 """A plain-integer restatement of the two stream-object state machines of the C ABI:
 ``filterbank_exec`` (pfb_filterbank_execute / _strided / _dada) and ``ifb_exec``
 (pfb_inverse_filterbank_execute / _strided / _dada) in
-ska-pst-dsp-model_amd/csrc/pfb_api.hip.
+ska-pst-dsp-model_amd/csrc/pfb_api_analysis.hip and pfb_api_synthesis.hip.
 
 No torch, no GPU, no test in here: given a plan's integers and a list of chunk lengths the
 functions return one record per call — which path the call takes, what it returns, what it
@@ -10,7 +10,8 @@ checks the model against what existing GPU tests assert and proves the reachabil
 one-launch path rests on; tests/test_gpu_stream_edges.py drives the plans through the sequence
 tables below and compares every call with the model.
 
-The comments name the restated line as file:line of csrc/pfb_api.hip unless they say otherwise.
+The comments name the function (and where useful the branch) of those two files that a line
+restates, unless they say otherwise.
 """
 from collections import namedtuple
 
@@ -25,16 +26,16 @@ SYNTHESIS_ENTRIES = ("packed", "strided", "dada", "host")
 
 
 def floordiv(a, b):
-    return a // b  # Python's // floors like pfb_api.hip's floordiv
+    return a // b  # Python's // floors like pfb_host.hpp's floordiv
 
 
 # ============================================================================ analysis
 class AnalysisShape(namedtuple("AnalysisShape", "variant N nu de P")):
-    """(variant, N, nu, de, P) of an analysis plan; P = ceil(n_taps / N) (:512)."""
+    """(variant, N, nu, de, P) of an analysis plan; P = ceil(n_taps / N) (analysis_validate)."""
 
     @property
     def M(self):
-        return (self.N * self.de) // self.nu  # :510
+        return (self.N * self.de) // self.nu  # analysis_validate
 
     @property
     def PN(self):
@@ -42,25 +43,25 @@ class AnalysisShape(namedtuple("AnalysisShape", "variant N nu de P")):
 
     @property
     def stream_kernel(self):
-        """stream_shape (csrc/pfb_analysis.hip:832-837): the N 256 streaming kernel."""
+        """stream_shape (csrc/pfb_analysis.hip): the N 256 streaming kernel."""
         return (self.variant == BUNTON and self.N == 256 and (self.nu, self.de) in ((8, 7), (4, 3))
                 and self.P in (12, 13))
 
     @property
     def fused(self):
-        """pfb_analysis_plan::fused (:517-521, analysis_supported csrc/pfb_analysis.hip:866-871)."""
+        """pfb_analysis_plan::fused (analysis_validate; analysis_supported, csrc/pfb_analysis.hip)."""
         if self.variant == LOWCBF:
             return True
         return 8 <= self.N <= 256 and self.N & (self.N - 1) == 0 and self.P <= 32
 
     @property
     def fused_takes_carry(self):
-        """analysis_fused_takes_carry (csrc/pfb_analysis.hip:885-889)."""
+        """analysis_fused_takes_carry (csrc/pfb_analysis.hip)."""
         return self.fused and not self.stream_kernel and self.variant != LOWCBF
 
     @property
     def window(self):
-        """The streaming kernel's first register window in samples (:843)."""
+        """The streaming kernel's first register window in samples (filterbank_exec, one-launch path: `win`)."""
         return (self.de * (16 // self.nu) + self.P) * self.N
 
     @property
@@ -71,12 +72,12 @@ class AnalysisShape(namedtuple("AnalysisShape", "variant N nu de P")):
 
 
 def analysis_K(shape, n_dat, pad_due=False):
-    """analysis_K (:458-468)."""
+    """analysis_K."""
     if shape.variant == LOWCBF:
-        return max(floordiv(n_dat + (1536 if pad_due else 0) - 3072, 192), 0)  # :459-461
+        return max(floordiv(n_dat + (1536 if pad_due else 0) - 3072, 192), 0)  # LowCBF branch
     if shape.variant == BUNTON:
-        return max(floordiv(n_dat - shape.PN, shape.M), 0)  # :463-465
-    return max(n_dat // shape.M, 0)  # :467
+        return max(floordiv(n_dat - shape.PN, shape.M), 0)  # Bunton branch
+    return max(n_dat // shape.M, 0)  # padded
 
 
 AnalysisCall = namedtuple(
@@ -84,29 +85,29 @@ AnalysisCall = namedtuple(
 
 
 def analysis_call(shape, B, n_in, entry="packed", pad_due=False):
-    """One filterbank_exec call on a state of B buffered samples (:797-1013).  Returns the
+    """One filterbank_exec call on a state of B buffered samples (its lengths: fb_lens).  Returns the
     record and the pad flag after the call."""
     assert entry in ANALYSIS_ENTRIES and n_in >= 0 and B >= 0
     device = entry != "host"
     sec = entry.startswith("dada")
     fus = entry == "dada_fused"
-    total = B + n_in  # :814
-    K = analysis_K(shape, total, pad_due)  # :833 / :887 / :952
-    Kt = K - K % shape.nu  # the nu trim, :834 / :888 / :954 (FilterBank.m:93-104)
-    input_idat = (Kt * shape.N * shape.de) // shape.nu  # :835 / :996 (FilterBank.m:119-126)
+    total = B + n_in  # fb_lens
+    K = analysis_K(shape, total, pad_due)  # fb_lens
+    Kt = K - K % shape.nu  # fb_lens: the nu trim (FilterBank.m:93-104)
+    input_idat = (Kt * shape.N * shape.de) // shape.nu  # fb_lens (FilterBank.m:119-126)
     pad = 0
-    if (device and 0 < B <= shape.window  # :847
-            and ((shape.variant == BUNTON and shape.stream_kernel) or (fus and shape.variant == LOWCBF))  # :848
-            and input_idat >= B and not pad_due and (not sec or fus)):  # :848-849
+    if (device and 0 < B <= shape.window  # filterbank_exec, one-launch path
+            and ((shape.variant == BUNTON and shape.stream_kernel) or (fus and shape.variant == LOWCBF))
+            and input_idat >= B and not pad_due and (not sec or fus)):
         path, pad = "one_launch", B
     elif (not sec and device and B > 0 and not pad_due and shape.fused and shape.fused_takes_carry
-          and input_idat >= B and Kt > 0):  # :894-895
+          and input_idat >= B and Kt > 0):  # filterbank_exec, fused-with-pre path
         path, pad = "fused_pre", B
-    elif B == 0 and device and (not sec or fus):  # :932
+    elif B == 0 and device and (not sec or fus):  # filterbank_exec, `in_place`
         path = "in_place"
     else:
         path = "concat"
-    carry_after = max(total - input_idat, 0)  # :861 / :917 / :997
+    carry_after = max(total - input_idat, 0)  # fb_lens nb, fb_carry
     via_pre = path in ("one_launch", "fused_pre")
     flags = set()
     if B > 0 and input_idat == B:
@@ -122,7 +123,7 @@ def analysis_call(shape, B, n_in, entry="packed", pad_due=False):
     if total > 0 and carry_after == 0:
         flags.add("empty_new_carry")
     if pad_due:
-        flags.add("pad_consumed")  # every accepted call consumes it, rows or not (:953-958)
+        flags.add("pad_consumed")  # every accepted call consumes it, rows or not (filterbank_exec: PadConsume::accept)
     rec = AnalysisCall(n_in, entry, B, K, Kt, input_idat, Kt, carry_after, path, pad, pad_due,
                        frozenset(flags))
     return rec, False
@@ -131,7 +132,7 @@ def analysis_call(shape, B, n_in, entry="packed", pad_due=False):
 def analysis_stream(shape, chunks, entries="packed"):
     """Records of a stream of calls from a fresh (or reset) plan.  ``entries``: one entry name
     for every call or one per call; a chunk given as the string "reset" is
-    pfb_filterbank_reset (:1019-1024) and yields no record."""
+    pfb_filterbank_reset and yields no record."""
     if isinstance(entries, str):
         entries = [entries] * len(chunks)
     B, pad_due, out = 0, shape.variant == LOWCBF, []
@@ -147,8 +148,8 @@ def analysis_stream(shape, chunks, entries="packed"):
 
 def analysis_dada_diag(rec):
     """pfb_analysis_last_dada_input after the call (include/pfb_api.h:386-400): 'none' after a
-    cf32 call; FUSED where the kernel read the section in place — nothing buffered (:959) or the
-    one-launch carry path — else STAGED (:813: unpacked behind the carry)."""
+    cf32 call; FUSED where the kernel read the section in place — nothing buffered (filterbank_exec, `in_place`) or the
+    one-launch carry path — else STAGED (filterbank_exec, concatenation: unpacked behind the carry)."""
     if not rec.entry.startswith("dada"):
         return "none"
     if rec.entry == "dada_fused" and rec.path in ("in_place", "one_launch"):
@@ -198,7 +199,7 @@ class SynthesisShape(namedtuple("SynthesisShape", "N nu de Nf Ov sample_offset")
 
 
 def synth_blocks(shape, n_dat):
-    """synth_blocks (:1090-1093)."""
+    """synth_blocks."""
     return max(floordiv(n_dat - 2 * shape.Ov, shape.keep), 0)
 
 
@@ -208,44 +209,44 @@ SynthesisCall = namedtuple(
 
 
 def synthesis_call(shape, Bc, n_in, entry="packed", spectral=False):
-    """One ifb_exec call on a state of Bc buffered rows (:1809-1979).  ``rows`` is the output
+    """One ifb_exec call on a state of Bc buffered rows (its lengths: ifb_lens).  ``rows`` is the output
     length in samples; a rejected call leaves the carry as it was."""
     assert entry in SYNTHESIS_ENTRIES and n_in >= 0 and Bc >= 0
-    total = Bc + n_in  # :1824
-    so = min(shape.sample_offset, total)  # :1826
-    B = synth_blocks(shape, total - so)  # :1828
+    total = Bc + n_in  # ifb_lens
+    so = min(shape.sample_offset, total)  # ifb_lens
+    B = synth_blocks(shape, total - so)  # ifb_lens
     full = B * shape.Lkeep
     input_idat = B * shape.keep
     buffered = total - input_idat
     olen = full
     flags = set()
-    rem = buffered % shape.nu  # :1833 (Python's % is already non-negative)
+    rem = buffered % shape.nu  # ifb_lens (Python's % is already non-negative)
     if rem:
-        # carry rounded up to a multiple of nu (InverseFilterBank.m:104-135), :1834-1838
+        # carry rounded up to a multiple of nu (InverseFilterBank.m:104-135), ifb_lens
         buffered += shape.nu - rem
         input_idat = total - buffered
         olen = min(max(0, floordiv(input_idat * shape.N * shape.de, shape.nu)), full)
         flags.add("rounded_carry")
     if n_in == 0 and Bc > 0:
         flags.add("zero_len_call")
-    if input_idat < 0:  # :1840
+    if input_idat < 0:  # ifb_exec: the call is rejected
         flags.discard("rounded_carry")
         return SynthesisCall(n_in, entry, Bc, B, input_idat, 0, full, Bc, "rejected", 0, 0,
                              frozenset(flags | {"rejected"}))
     if olen < full:
         flags.add("olen_lt_full")
     b_s = stitched_new = 0
-    if entry != "host" and Bc > 0 and not spectral and input_idat >= Bc:  # :1904
+    if entry != "host" and Bc > 0 and not spectral and input_idat >= Bc:  # ifb_exec, split path
         if olen > 0:
-            # first block that starts at or after row Bc of the concatenation, :1907
+            # first block that starts at or after row Bc of the concatenation (ifb_exec, split path: b_s)
             b_s = min(B, max(0, (Bc - so + shape.keep - 1) // shape.keep))
             if b_s > 0:
-                L = min(total, so + (b_s - 1) * shape.keep + shape.Nf)  # :1909
+                L = min(total, so + (b_s - 1) * shape.keep + shape.Nf)  # the stitched buffer's rows
                 stitched_new = max(L - Bc, 0)
         path = "split(%d, %d)" % (b_s, B)
         if input_idat == Bc:
             flags.add("idat_eq_carry")
-    elif Bc == 0 and entry != "host":  # :1933
+    elif Bc == 0 and entry != "host":  # ifb_exec, in-place branch
         path = "in_place"
     else:
         path = "concat"
@@ -272,11 +273,11 @@ def synthesis_stream(shape, chunks, entries="packed", spectral=False):
 def synthesis_diag(rec, reads_in_place=True):
     """(last_strided_input, last_dada_input) after an ACCEPTED call (include/pfb_api.h:354-356,
     437-439).  ``reads_in_place``: the plan's channel IFFT can read the layout / the section
-    itself (strided_in_place / dada_fusable, :1680, :1647); otherwise every strided or DADA call
-    is staged whole (:1864, :1876).  In place where any block of new rows is read through the
+    itself (strided_in_place / dada_fusable); otherwise every strided or DADA call
+    is staged whole (ifb_exec: strided_stage, dada_stage).  In place where any block of new rows is read through the
     entry (blocks [b_s, B) of the split path, every block with nothing buffered); staged where
-    only the copy kernel touched the new rows (stitched head, carry, concatenation: rows_to,
-    :1883-1897); none where nothing of the entry was read."""
+    only the copy kernel touched the new rows (stitched head, carry, concatenation: ifb_exec's
+    rows_to); none where nothing of the entry was read."""
     if rec.entry not in ("strided", "dada"):
         return "none", "none"
     if not reads_in_place:
@@ -284,7 +285,7 @@ def synthesis_diag(rec, reads_in_place=True):
     elif rec.path == "in_place":
         d = "in_place" if rec.rows > 0 else "staged" if rec.carry_after > 0 else "none"
     elif rec.path == "concat":
-        d = "staged"  # rows_to runs for every concatenation, :1955
+        d = "staged"  # rows_to runs for every concatenation (ifb_exec)
     else:
         if rec.rows > 0 and rec.b_s < rec.blocks:
             d = "in_place"

@@ -222,8 +222,8 @@ VARIANTS = ["polyphase_analysis", "polyphase_analysis_padded"]
 @pytest.mark.parametrize("variant", VARIANTS)
 def test_analysis_fused_kernel_layout(gpu, variant):
     """N 8, 8/7, 81 taps (P 11), n_dat 4101: the fused one-launch kernel —
-    analysis_supported sets `fused` for 8 <= N <= 256 (pfb_analysis.hip:780-785) and
-    launch_analysis takes launch_fused_v<8> (:833-842), P 11 exact instance (:764)."""
+    analysis_supported sets `fused` for 8 <= N <= 256 (pfb_analysis.hip) and
+    launch_analysis takes launch_fused_v<8>, P 11 exact instance (launch_fused_p)."""
     pfb = _pfb()
     taps = pfb.design_PFB_FIR_filter(8, "8/7", 10)
     assert len(taps) == 81
@@ -234,9 +234,9 @@ def test_analysis_fused_kernel_layout(gpu, variant):
 @pytest.mark.parametrize("variant", VARIANTS)
 def test_analysis_streaming_kernel_layout(gpu, variant, os_):
     """N 256, 3073 taps (P 13), n_dat 2^16 + 3.  Bunton: the streaming kernel — stream_shape
-    (pfb_analysis.hip:746-751: N 256, Bunton, (nu 8, M 224) or (nu 4, M 192), P 12/13) makes
-    launch_analysis take launch_stream_any (:827-832).  Padded: stream_shape is false, so
-    the same shape runs the fused one-launch kernel launch_fused_v<256> (:833-842)."""
+    (pfb_analysis.hip: N 256, Bunton, (nu 8, M 224) or (nu 4, M 192), P 12/13) makes
+    launch_analysis take launch_stream_any.  Padded: stream_shape is false, so
+    the same shape runs the fused one-launch kernel launch_fused_v<256>."""
     pfb = _pfb()
     taps = pfb.design_PFB_FIR_filter(256, os_, 12)
     assert len(taps) == 3073
@@ -246,9 +246,9 @@ def test_analysis_streaming_kernel_layout(gpu, variant, os_):
 @pytest.mark.parametrize("variant", VARIANTS)
 def test_analysis_fir_lds_row_fft_layout(gpu, variant):
     """N 512, 8/7, 12 taps per channel (P 13), n_dat 60 037: not fused (N > 256,
-    pfb_analysis.hip:782), so FIR into scratch + row FFT (:846-880); the FIR is
-    fir_lds_kernel: fir_window_applies (:634-639, DE 7, P in [7, 32]) and NU 8 divides the
-    workgroup (:617-624)."""
+    analysis_supported), so FIR into scratch + row FFT (launch_analysis, generic branch); the FIR is
+    fir_lds_kernel: fir_window_applies (DE 7, P in [7, 32]) and NU 8 divides the
+    workgroup (fir_lds_shape)."""
     pfb = _pfb()
     taps = pfb.design_PFB_FIR_filter(512, "8/7", 12)
     _analysis_case(gpu, taps, 512, "8/7", variant, 60037, 2, 103, _orc_analysis(taps, 512, "8/7", variant))
@@ -256,9 +256,9 @@ def test_analysis_fir_lds_row_fft_layout(gpu, variant):
 
 def test_analysis_fir_window_layout(gpu):
     """N 512, 32/27, padded, 28 taps per channel (P 29): the register-window FIR
-    fir_window_kernel — fir_window_applies needs DE 27 <= P <= 32 (pfb_analysis.hip:634-639;
+    fir_window_kernel — fir_window_applies needs DE 27 <= P <= 32 (pfb_analysis.hip;
     12 taps per channel, P 13 < DE, would run fir_generic_kernel) and DE 27 has no LDS form
-    (:617, :627-630)."""
+    (fir_lds_shape)."""
     pfb = _pfb()
     taps = pfb.design_PFB_FIR_filter(512, "32/27", 28)
     assert -(-len(taps) // 512) == 29
@@ -268,7 +268,7 @@ def test_analysis_fir_window_layout(gpu):
 
 def test_analysis_lowcbf_layout(gpu):
     """PFB_ANALYSIS_LOWCBF with PST_filtertaps.txt, n_dat 3072 + 192 * 20 + 7: analysis_run
-    launches launch_lowcbf (pfb_api.hip:268-284), 216 output channels, the 1536 leading zeros
+    launches launch_lowcbf (its LowCBF branch), 216 output channels, the 1536 leading zeros
     of the plan's first call (restored by pfb_filterbank_reset before every call here)."""
     pfb = _pfb()
     taps = pfb.read_fir_filter_coeff(pfb.config.config_dir + "/PST_filtertaps.txt")
@@ -286,7 +286,7 @@ def test_analysis_4096_odd_row_count(gpu, variant, n_pol):
     n_rows >= 2 (pfb_rowfft.hip:354-361, the `if constexpr (!GAIN)` block of launch_row_fft_t), whose
     last workgroup has a row A without a row B: row A's values, the skipped r4k_row of row B
     and — with two pols — pol 0's last pair next to pol 1's first row in the exactly sized
-    scratch (pfb_api.hip, analysis_run).  Row B's loads of that last pair are pointed at
+    scratch (analysis_run).  Row B's loads of that last pair are pointed at
     row A (they used to read past the last row through the scalar offset, which the buffer
     range check does not cover; the values are discarded, so no value test can see that
     read — this test checks the values of the odd-count branch only)."""
@@ -364,9 +364,9 @@ def _filterbank_case(dev, taps, N, os_, variant, chunks, out_layout, seed, n_pol
 @pytest.mark.parametrize("os_", ["8/7", "4/3"])
 def test_filterbank_streaming_carry_layout(gpu, os_):
     """N 256 Bunton, three ragged chunks: the first call reads the input in place
-    (pfb_api.hip:776-841, filterbank_exec's generic branch), the later ones carry B <= (DE 16/NU + P) N
+    (filterbank_exec, concatenate-or-in-place path), the later ones carry B <= (DE 16/NU + P) N
     samples and take the one-launch carry path of the streaming kernel (the
-    `analysis_offset_ok && input_idat >= B` branch, pfb_api.hip:676-706, carry read through
+    `analysis_offset_ok && input_idat >= B` branch: filterbank_exec, one-launch path; carry read through
     AnalysisArgs::pre).
     Input framed with a gap, capacity larger than T_out, out_pol_stride larger than
     capacity x n_chan.  Bunton computes only the kept rows: no scratch rows anywhere."""
@@ -391,11 +391,11 @@ PADDED_LAYOUTS = {
 @pytest.mark.parametrize("layout", list(PADDED_LAYOUTS))
 def test_filterbank_padded_fused_carry_layout(gpu, layout):
     """N 16, 8/7, 10 taps per channel, padded, chunks 1000 / 1500 / 777: K 71 with T_out 64
-    on the first call (filterbank_exec's generic branch, pfb_api.hip:776-841, input in place), K 114 with T_out 112
+    on the first call (filterbank_exec, concatenate-or-in-place path, input in place), K 114 with T_out 112
     on the second with a carry of 104 <= input_idat (the fused-carry branch:
-    `p->fused && analysis_fused_carry_ok(p) && input_idat >= B`, pfb_api.hip:743-773), K 58 / T_out 56 on the third.
+    `p->fused && analysis_fused_carry_ok(p) && input_idat >= B`: filterbank_exec, fused-with-pre path), K 58 / T_out 56 on the third.
     All K rows are computed (the circular shift); they go straight into the caller's buffer
-    only when capacity >= K AND out_pol_stride >= K n_chan (:753, :816), else through stage_out."""
+    only when capacity >= K AND out_pol_stride >= K n_chan (fb_rows_dst), else through stage_out."""
     pfb = _pfb()
     taps = pfb.design_PFB_FIR_filter(16, "8/7", 10)
     seen = _filterbank_case(gpu, taps, 16, "8/7", "polyphase_analysis_padded", (1000, 1500, 777),
@@ -406,7 +406,7 @@ def test_filterbank_padded_fused_carry_layout(gpu, layout):
 @pytest.mark.parametrize("layout", list(PADDED_LAYOUTS))
 def test_filterbank_padded_generic_layout(gpu, layout):
     """N 512, 8/7, padded: not fused (N > 256), so every call concatenates carry + input and
-    takes filterbank_exec's generic branch (pfb_api.hip:776-841; FIR + row FFT over all K rows): K 44 / 79 / 42
+    takes filterbank_exec's concatenate-or-in-place path (FIR + row FFT over all K rows): K 44 / 79 / 42
     with T_out 40 / 72 / 40.  The same three layouts."""
     pfb = _pfb()
     taps = pfb.design_PFB_FIR_filter(512, "8/7", 12)
@@ -562,7 +562,7 @@ def test_synthesis_block_kernel_layout(gpu):
 def test_synthesis_wave_kernel_layout(gpu):
     """N 256, Nf 256, Ov 48, 8/7 (W 224, keep 160): synth_wave_supported
     (pfb_synth_wave.hip:34-39) makes synthesis_chunk write the stage-1 rows in 2-row runs
-    (pfb_api.hip:1010, `zb`) and launch_synth_block take synth_wave_kernel (pfb_synth.hip:242).
+    (synthesis_chunk, `l.zblk`) and launch_synth_block take synth_wave_kernel (pfb_synth.hip:242).
     Six blocks plus a ragged tail."""
     _synthesis_case(gpu, 256, "8/7", 256, 48, 6 * 160 + 96 + 5, 302)
 
@@ -575,7 +575,7 @@ def test_synthesis_wave512_kernel_layout(gpu):
 
 def test_synthesis_spectral_taper_layout(gpu):
     """N 8, Nf 128, Ov 16 with the `hann` spectral taper: synthesis_chunk's has_spectral
-    branch (pfb_api.hip:987-991, synthesis_spectral: per-channel FFT, stitch x taper, row IFFTs)."""
+    branch (synthesis_spectral: per-channel FFT, stitch x taper, row IFFTs)."""
     _synthesis_case(gpu, 8, "8/7", 128, 16, 5 * 96 + 32 + 7, 304, spectral="hann")
 
 
@@ -593,7 +593,7 @@ def _ifb_exec(lib, plan, fin, n_in, fout, cap, dev, mem=DEVICE):
 def test_inverse_filterbank_layout(gpu, N, nf, ov, chunks):
     """pfb_inverse_filterbank_execute over three chunks, framed against contiguous: the first
     call reads the input in place, the later ones carry rows and take the in-place carry
-    path (`Bc > 0 && !has_spectral && input_idat >= Bc`, pfb_api.hip:1522-1549): the first blocks from a stitched
+    path (`Bc > 0 && !has_spectral && input_idat >= Bc`: ifb_exec, split path): the first blocks from a stitched
     buffer of carry + input head, the rest from the input with a row shift.  There is no
     length query for this entry point: *n_out must equal the InverseFilterBank.m oracle's
     length, which is also the contiguous run's exact stride and capacity."""
@@ -715,7 +715,7 @@ def test_roundtrip_chunked_layout(gpu):
 
 def test_roundtrip_fused_fir_layout(gpu):
     """N 512, 8/7, Nf 128, Ov 16: the fused path of the generic analysis (roundtrip_run's
-    `!pa->fused` arm, pfb_api.hip:1773-1778: the FIR writes the stage-1 rows, the row FFT makes the channelised
+    `!pa->fused` arm of its fused path: the FIR writes the stage-1 rows, the row FFT makes the channelised
     product from them, the block kernel reads them)."""
     _roundtrip_case(gpu, 512, 12, 128, 16, 200003, 4, 403)
 

@@ -10,7 +10,7 @@ C ABI's profiler (pfb_profile_enable / pfb_profile_kernel_name, _lib.py), which 
 demangled name of the last single-kernel launch of class 0 (analysis), 1 (channel IFFT)
 and 2 (block or wave kernel); each case asserts the template and the leading template
 arguments it claims to cover.  Paths of several launches record no name (ProfScope,
-pfb_api.hip, single = false): the non-fused analysis (FIR + row FFT: families B and C) and
+pfb_host.hpp, single = false): the non-fused analysis (FIR + row FFT: families B and C) and
 the spectral-taper synthesis (six launches per polarisation: family F).  Their cases
 assert exactly that — one multi-launch record in the class and no single-kernel name, i.e.
 neither the fused analysis kernel nor the channel-IFFT / block / wave kernels ran — and

@@ -485,7 +485,7 @@ def test_filterbank_stream_padded(gpu):
     100 353 two-stage taps, 8/7 (FilterBank.m:85-126 calling polyphase_analysis_padded).
     The Matlab object calls the padded analysis on carry + chunk every time, so each call
     restarts the commutator with zero history (polyphase_analysis_padded.m:101-102) and
-    circularly shifts its own rows by -sds (:156) — the reference defect SURVEY §8(c)
+    circularly shifts its own rows by -sds (polyphase_analysis_padded.m:156) — the reference defect SURVEY §8(c)
     names; the engine reproduces it by running the analysis over the concatenated call
     input (pfb_filterbank_execute: all K rows, the nu-trimmed Kt copied out).  Chunks are
     shorter than M (3584: no output row, everything carried), shorter and longer than
@@ -573,7 +573,7 @@ def test_inverse_filterbank_stream_carry_in_place(gpu, N, nf, ov, chunks):
 def test_inverse_filterbank_sample_offset_matches_oracle(gpu, N, nf, ov, so, chunks, device):
     """InverseFilterBank.sample_offset != 0 (InverseFilterBank.m:12,92-96): every call
     synthesises the concatenated carry + input from row sample_offset on, and the carry
-    starts at the consumed blocks' end (:104-133) — against InverseFilterBankOracle (its
+    starts at the consumed blocks' end (InverseFilterBank.m:104-133) — against InverseFilterBankOracle (its
     literal restatement) over several chunkings, host and device inputs, with the carry
     in place (row shift) and stitched."""
     import torch
@@ -671,7 +671,7 @@ def test_synthesis_spectral_custom_and_combine(gpu):
 def test_inverse_filterbank_sample_offset_spectral_taper(gpu, so, chunks, device):
     """sample_offset != 0 together with frequency_taper('hann') (InverseFilterBank.m:48-61,
     92-96): the spectral-taper path takes the offset as a negative row shift into the
-    concatenated carry + input (pfb_api.hip synthesis_chunk) — against
+    concatenated carry + input (synthesis_chunk, has_spectral branch) — against
     InverseFilterBankOracle over several chunks, host and device input."""
     import torch
     pfb = _pfb()
@@ -729,7 +729,7 @@ def test_inverse_filterbank_frequency_taper_stream(gpu):
 def test_synthesis_fractional_output_overlap(gpu, N, os_, nf, ov, spans):
     """output_overlap = normalize(os, Ov) * n_chan (polyphase_synthesis.m:117) need not be a
     multiple of n_chan: the kept samples iFFFF(output_overlap + 1 : L - output_overlap)
-    (:302) then start mid-way through a t1 row.  The kernels discard sample-exactly
+    (polyphase_synthesis.m:302) then start mid-way through a t1 row.  The kernels discard sample-exactly
     (offset t0 + N t1 - L_ov, range-checked)."""
     import torch
     pfb = _pfb()

@@ -313,7 +313,7 @@ def _stream_chunks(plan, twin, chunks_d, S, cu, regime, nu, win_lo, win_hi, M, k
         _assert_partition(regime, steps, RANGES["stream"](cu, S, steps), f"{what} chunk {i} ({rows} rows)")
         _assert_single(steps, RANGES["stream"](cu, 3, steps), f"{what} chunk {i}")
         if i and win_lo is not None:
-            # the one-launch carry path of filterbank_exec (pfb_api.hip): the carried samples
+            # the one-launch carry path of filterbank_exec (its one-launch path): the carried samples
             # lie in the kernel's first window (read through AnalysisArgs::pre), more of them
             # than P N, and the kernel copies the next carry itself (carry_out)
             assert win_lo < B <= win_hi and rows * M >= B, (i, B, win_lo, win_hi)

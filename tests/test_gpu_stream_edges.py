@@ -1,5 +1,5 @@
 """Stream objects at the boundaries of their carry paths (filterbank_exec and ifb_exec,
-ska-pst-dsp-model_amd/csrc/pfb_api.hip), through every entry point of the C ABI.
+ska-pst-dsp-model_amd/csrc/pfb_api_analysis.hip and pfb_api_synthesis.hip), through every entry point of the C ABI.
 
 tests/stream_model.py restates the two host state machines in integers and holds the call
 sequences; tests/test_stream_model.py proves on the CPU that each sequence sits on the edges

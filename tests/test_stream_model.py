@@ -1,5 +1,5 @@
 """CPU checks of tests/stream_model.py, the integer restatement of filterbank_exec and ifb_exec
-(ska-pst-dsp-model_amd/csrc/pfb_api.hip):
+(ska-pst-dsp-model_amd/csrc/pfb_api_analysis.hip, pfb_api_synthesis.hip):
 
   * it reproduces what the GPU suite already asserts of the real plans (the carries of
     test_gpu_strided_synthesis.py, the DADA paths of test_gpu_dada_analysis.py);
@@ -50,7 +50,7 @@ def test_model_reproduces_dada_analysis_stream(shape):
 
 def test_model_lowcbf_pad_is_consumed_by_a_rowless_call():
     """analysis_K adds the 1536 pre-pad while it is due; the first accepted call consumes it even
-    when it returns no rows (pfb_api.hip: PadConsume::accept before the Kt > 0 branch)."""
+    when it returns no rows (filterbank_exec: PadConsume::accept before the Kt > 0 branch)."""
     s = sm.LOWCBF_SHAPE
     assert sm.analysis_K(s, 1000, True) == 0 and sm.analysis_K(s, 1536 + 192, True) == 1
     recs = sm.analysis_stream(s, (1000, 2072))
