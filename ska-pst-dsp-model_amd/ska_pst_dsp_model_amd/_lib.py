@@ -51,10 +51,8 @@ PFB_STRIDED_INPUT_NONE = 0
 PFB_STRIDED_INPUT_IN_PLACE = 1
 PFB_STRIDED_INPUT_STAGED = 2
 
-_STATUS_NAMES = {
-    0: "PFB_OK", 1: "PFB_ERR_INVALID_ARG", 2: "PFB_ERR_UNSUPPORTED", 3: "PFB_ERR_HIP",
-    4: "PFB_ERR_OOM", 5: "PFB_ERR_BUFFER_TOO_SMALL", 6: "PFB_ERR_NO_DEVICE",
-}
+_STATUS_NAMES = {value: name for name, value in list(globals().items())
+                 if name == "PFB_OK" or name.startswith("PFB_ERR_")}
 
 
 class PfbError(RuntimeError):

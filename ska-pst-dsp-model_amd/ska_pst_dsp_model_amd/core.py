@@ -17,14 +17,13 @@ goes through the HIP kernels of ``libpfb_hip.so``; there is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes
 import hashlib
 from ctypes import byref, c_int64, c_void_p
 
 import numpy as np
 
 from . import _lib
-from .config import Rational, as_rational
+from .config import as_rational
 from .window import PFBWindow, Taper, identity_taper
 
 __all__ = ["AnalysisPlan", "SynthesisPlan", "polyphase_analysis", "polyphase_analysis_padded",
@@ -61,7 +60,7 @@ def _capturing(plan) -> bool:
     """Is a stream capture that recorded launches of ``plan`` still active?"""
     t = _torch()
     live = []
-    for s in getattr(plan, "_capture_streams", ()):
+    for s in plan._capture_streams:
         with t.cuda.stream(s):
             if t.cuda.is_current_stream_capturing():
                 live.append(s)
@@ -69,13 +68,17 @@ def _capturing(plan) -> bool:
     return bool(live)
 
 
-def _close_guard(plan):
-    # A captured graph references the plan's device buffers (taps, twiddles, stage-1 rows,
-    # carry) by address: freeing them while the capture is open, or before every graph that
-    # replays them is gone, makes the replays read freed memory.
-    if getattr(plan, "_capture_streams", None) and _capturing(plan):
-        raise RuntimeError(f"{type(plan).__name__}.close(): a stream capture that used this plan is "
-                           "still active; end the capture (and drop its graphs) first")
+def _keep_alive(plan, tensor, device):
+    """Keep ``tensor`` alive for the launches just enqueued on ``device``'s current stream,
+    which read it (it may be a temporary: a ``.contiguous()`` or ``_prep_in`` copy).  Outside a
+    capture its memory may be reused only after that work has finished (``record_stream``).
+    A captured launch holds the address for every replay: the plan then keeps the tensor as
+    long as it lives (one entry per address, so recaptures do not grow it)."""
+    t = _torch()
+    if t.cuda.is_current_stream_capturing():
+        plan._graph_inputs[tensor.data_ptr()] = tensor
+    else:
+        tensor.record_stream(t.cuda.current_stream(device))
 
 
 def _taps64(filt) -> np.ndarray:
@@ -84,14 +87,100 @@ def _taps64(filt) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(filt, dtype=np.float64).ravel())
 
 
+# ============================================================================ sizes and names
+_SECTION_TYPES = {8: "int8", 16: "int16", 32: "float32", 64: "float64"}
+
+
+def _section_samples(raw, values: int, nbit: int, ndim: int, lowcbf: bool) -> int:
+    """Time samples the section tensor ``raw`` holds, at ``values`` numbers of ``ndim``
+    components of ``nbit`` bits per sample (n_pol for a single-channel section, n_chan * n_pol
+    for a channelised one), as ``layout.dada_unpack`` infers them: whole samples, and whole
+    heaps of 32 of a LowCBF section.  0 for a format the C ABI rejects."""
+    if int(nbit) not in _SECTION_TYPES or int(ndim) not in (1, 2):
+        return 0
+    n_dat = (raw.numel() * raw.element_size()) // (values * int(ndim) * (int(nbit) // 8))
+    return n_dat - n_dat % 32 if lowcbf else n_dat
+
+
+def _section(raw, who: str, values: int, nbit: int, ndim: int, lowcbf: bool):
+    """-> (the section, contiguous; its ``_section_samples``).  The DADA entries are
+    device-only: a host array is answered as the C ABI would."""
+    if not is_device_array(raw):
+        raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, f"{who}: expects a device tensor")
+    raw = raw.contiguous()
+    return raw, _section_samples(raw, values, nbit, ndim, lowcbf)
+
+
+def _alloc_section(shape, nbit: int, device):
+    """-> (device tensor of the DADA sample type, its bytes); a format the C ABI rejects gets
+    an empty byte tensor to stand in."""
+    t = _torch()
+    if int(nbit) not in _SECTION_TYPES:
+        return t.empty((0,) + tuple(shape[1:]), dtype=t.int8, device=device), 0
+    sec = t.empty(tuple(max(int(v), 0) for v in shape), dtype=getattr(t, _SECTION_TYPES[int(nbit)]),
+                  device=device)
+    return sec, sec.numel() * sec.element_size()
+
+
+def _order(lowcbf: bool) -> int:
+    return _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
+
+
+# what the plans' last_* getters report (anything else, 0 and -1 included: 'none')
+_DADA_INPUT_NAMES = {_lib.PFB_DADA_INPUT_FUSED: "fused", _lib.PFB_DADA_INPUT_STAGED: "staged"}
+_DADA_OUTPUT_NAMES = {_lib.PFB_DADA_OUTPUT_FUSED: "fused", _lib.PFB_DADA_OUTPUT_STAGED: "staged"}
+_STRIDED_INPUT_NAMES = {_lib.PFB_STRIDED_INPUT_IN_PLACE: "in_place",
+                        _lib.PFB_STRIDED_INPUT_STAGED: "staged"}
+_STAGE1_NAMES = {_lib.PFB_STAGE1_STORED: "stored", _lib.PFB_STAGE1_RECOMPUTED: "recomputed"}
+
+
+def _mode_name(plan, getter: str, names: dict) -> str:
+    return names.get(int(getattr(plan._lib, getter)(plan._h)), "none")
+
+
+class _Plan:
+    """What the two plan classes share: the C handle and its lifetime."""
+
+    _destroy = None  # the subclass's pfb_*_plan_destroy
+
+    def __init__(self):
+        # first, before anything can raise: a constructor that fails leaves an object whose
+        # __del__ finds every attribute close() reads
+        self._h = None
+        self._capture_streams = []  # streams that captured launches of this plan
+        self._rt_input = None       # the input of a split round trip in flight (roundtrip_analysis)
+        self._graph_inputs = {}     # tensors that captured launches read, by address (_keep_alive)
+        self._lib = _lib.load()
+        _lib.require_device()
+
+    def close(self):
+        if self._h:
+            # A captured graph references the plan's device buffers (taps, twiddles, stage-1
+            # rows, carry) by address: freeing them while the capture is open, or before every
+            # graph that replays them is gone, makes the replays read freed memory
+            # (INTEGRATION.md §3).
+            if self._capture_streams and _capturing(self):
+                raise RuntimeError(f"{type(self).__name__}.close(): a stream capture that used this "
+                                   "plan is still active; end the capture (and drop its graphs) first")
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ============================================================================ analysis
-class AnalysisPlan:
+class AnalysisPlan(_Plan):
     """Device plan of one analysis filter bank (owns taps, twiddles, carry-over)."""
+
+    _destroy = "pfb_analysis_plan_destroy"
 
     def __init__(self, taps, n_chan: int, os_factor, variant: str = "polyphase_analysis",
                  n_pol: int = 1, device: int = 0):
-        lib = _lib.load()
-        _lib.require_device()
+        super().__init__()
         self.os_factor = as_rational(os_factor)
         self.n_chan = int(n_chan)
         self.n_pol = int(n_pol)
@@ -109,25 +198,11 @@ class AnalysisPlan:
         d = _lib.AnalysisDesc(v[variant], self.n_chan, self.os_factor.nu, self.os_factor.de,
                               ptr, len(arr), self.n_pol, self.device)
         h = c_void_p()
-        _lib.check(lib.pfb_analysis_plan_create(byref(d), byref(h)))
+        _lib.check(self._lib.pfb_analysis_plan_create(byref(d), byref(h)))
         self._h = h
-        self._capture_streams = []  # streams that captured launches of this plan
-        self._lib = lib
-        self.out_chan = int(lib.pfb_analysis_output_channels(h))  # 216 for LowCBF
+        self.out_chan = int(self._lib.pfb_analysis_output_channels(h))  # 216 for LowCBF
         self.step = (self.n_chan * self.os_factor.de) // self.os_factor.nu
         self.phases = -(-len(self.taps) // self.n_chan)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _close_guard(self)
-            self._lib.pfb_analysis_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def output_length(self, n_dat: int) -> int:
         return int(self._lib.pfb_analysis_output_length(self._h, int(n_dat)))
@@ -197,16 +272,36 @@ class AnalysisPlan:
                            device=like.device)
         return np.empty((self.n_pol, max(rows, 0), self.out_chan), dtype=np.complex64)
 
+    # Two row-capacity rules, different on purpose (keep both):
+    #
+    # _buffer_rows, the cf32 calls.  A stateful call returns Kt = K - K % nu rows of the K the
+    # buffered and new samples make, but a padded plan COMPUTES all K: its circular shift runs
+    # over every row (filterbank_exec: Krun = K).  The launch stores straight into the caller's
+    # buffer only when that has room for all Krun rows, rows [Kt, K) being scratch; otherwise it
+    # goes through the plan's staging buffer and a copy of Kt rows (fb_rows_dst).  K is at most
+    # (buffered + n) // step (the padded plan's own count; the others' is smaller), so one row
+    # more than that always has the room.
+    #
+    # _section_rows, the to-DADA calls.  The section gets exactly the Kt rows returned
+    # (pfb_filterbank_output_rows = fb_lens().Kt) and never scratch rows: analysis_to_dada has
+    # the store kernel write rows below Kt only, or runs the cf32 path into the plan's own K-row
+    # buffer and packs Kt rows from it, and checks the section's bytes against Kt rows alone.
+    # (pfb_filterbank_execute_strided drops rows [Kt, K) at the store in the same way.)
+    def _buffer_rows(self, n_dat: int, stateful: bool) -> int:
+        if stateful:
+            return (self.buffered_samples + n_dat) // max(self.step, 1) + 1
+        return self.output_length(n_dat)
+
+    def _section_rows(self, n_dat: int, stateful: bool) -> int:
+        return self.stream_rows(n_dat) if stateful else self.output_length(n_dat)
+
     def execute(self, x, stateful: bool = False):
         """Run the analysis; returns the (n_pol, K, n_chan) buffer (time-major)."""
         x, dev = self._prep_in(x)
         if x.shape[0] != self.n_pol:
             raise ValueError(f"plan built for n_pol={self.n_pol}, got {x.shape[0]}")
         n_dat = x.shape[1]
-        if stateful:
-            cap = (self.buffered_samples + n_dat) // max(self.step, 1) + 1
-        else:
-            cap = self.output_length(n_dat)
+        cap = self._buffer_rows(n_dat, stateful)
         out = self._alloc_out(x, dev, cap)
         n_out = c_int64(0)
         if dev:
@@ -229,24 +324,12 @@ class AnalysisPlan:
         (pfb_analysis_execute_dada / pfb_filterbank_execute_dada; ``last_dada_input()``
         tells).  n_dat is inferred as ``layout.dada_unpack`` does.  Returns the
         (n_pol, K, n_chan) buffer like ``execute``."""
-        if not is_device_array(raw):
-            raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "execute_dada: expects a device tensor")
-        raw = raw.contiguous()
-        if int(nbit) not in (8, 16, 32, 64) or int(ndim) not in (1, 2):
-            n_dat = 0  # (the C ABI rejects the format)
-        else:
-            n_dat = (raw.numel() * raw.element_size()) // (self.n_pol * int(ndim) * (int(nbit) // 8))
-            if lowcbf:
-                n_dat -= n_dat % 32
-        if stateful:
-            cap = (self.buffered_samples + n_dat) // max(self.step, 1) + 1
-        else:
-            cap = self.output_length(n_dat)
+        raw, n_dat = _section(raw, "execute_dada", self.n_pol, nbit, ndim, lowcbf)
+        cap = self._buffer_rows(n_dat, stateful)
         out = self._alloc_out(raw, True, cap)
         n_out = c_int64(0)
-        order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
         fn = self._lib.pfb_filterbank_execute_dada if stateful else self._lib.pfb_analysis_execute_dada
-        _lib.check(fn(self._h, c_void_p(raw.data_ptr()), int(nbit), int(ndim), order, n_dat,
+        _lib.check(fn(self._h, c_void_p(raw.data_ptr()), int(nbit), int(ndim), _order(lowcbf), n_dat,
                       c_void_p(out.data_ptr()), cap * self.out_chan, cap, byref(n_out), _stream_of(raw, self)))
         return out[:, :n_out.value, :]
 
@@ -254,19 +337,7 @@ class AnalysisPlan:
         """How the plan's last DADA call read its section: 'fused' (the analysis kernel
         loaded the file's own bytes), 'staged' (unpacked first), 'none' (no DADA call, or a
         cf32 call since) — pfb_analysis_last_dada_input."""
-        m = int(self._lib.pfb_analysis_last_dada_input(self._h))
-        return {_lib.PFB_DADA_INPUT_FUSED: "fused", _lib.PFB_DADA_INPUT_STAGED: "staged"}.get(m, "none")
-
-    def _alloc_section(self, like, rows: int, out_nbit: int):
-        """-> (device tensor (rows, out_chan, n_pol, 2) of the DADA sample type, its bytes)."""
-        t = _torch()
-        types = {8: t.int8, 16: t.int16, 32: t.float32, 64: t.float64}
-        if int(out_nbit) not in types:
-            # (the C ABI rejects the format; a byte tensor stands in)
-            return t.empty((0, self.out_chan, self.n_pol, 2), dtype=t.int8, device=like.device), 0
-        sec = t.empty((max(rows, 0), self.out_chan, self.n_pol, 2), dtype=types[int(out_nbit)],
-                      device=like.device)
-        return sec, sec.numel() * sec.element_size()
+        return _mode_name(self, "pfb_analysis_last_dada_input", _DADA_INPUT_NAMES)
 
     def execute_to_dada(self, x, out_nbit: int, scale: float = 1.0, stateful: bool = False):
         """The analysis of device series ``x`` written as a DADA data section: bit for bit
@@ -281,8 +352,8 @@ class AnalysisPlan:
         if x.shape[0] != self.n_pol:
             raise ValueError(f"plan built for n_pol={self.n_pol}, got {x.shape[0]}")
         n_dat = x.shape[1]
-        rows = self.stream_rows(n_dat) if stateful else self.output_length(n_dat)
-        sec, nbytes = self._alloc_section(x, rows, out_nbit)
+        sec, nbytes = _alloc_section((self._section_rows(n_dat, stateful), self.out_chan, self.n_pol, 2),
+                                     out_nbit, x.device)
         n_out = c_int64(0)
         fn = self._lib.pfb_filterbank_execute_to_dada if stateful else self._lib.pfb_analysis_execute_to_dada
         _lib.check(fn(self._h, c_void_p(x.data_ptr()), n_dat, n_dat, c_void_p(sec.data_ptr()), int(out_nbit),
@@ -295,22 +366,13 @@ class AnalysisPlan:
         bytes in, file bytes out (pfb_analysis_execute_dada_to_dada /
         pfb_filterbank_execute_dada_to_dada); ``last_dada_input()`` and
         ``last_dada_output()`` tell which sides the kernel read and wrote in place."""
-        if not is_device_array(raw):
-            raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "execute_dada_to_dada: expects a device tensor")
-        raw = raw.contiguous()
-        if int(nbit) not in (8, 16, 32, 64) or int(ndim) not in (1, 2):
-            n_dat = 0  # (the C ABI rejects the format)
-        else:
-            n_dat = (raw.numel() * raw.element_size()) // (self.n_pol * int(ndim) * (int(nbit) // 8))
-            if lowcbf:
-                n_dat -= n_dat % 32
-        rows = self.stream_rows(n_dat) if stateful else self.output_length(n_dat)
-        sec, nbytes = self._alloc_section(raw, rows, out_nbit)
+        raw, n_dat = _section(raw, "execute_dada_to_dada", self.n_pol, nbit, ndim, lowcbf)
+        sec, nbytes = _alloc_section((self._section_rows(n_dat, stateful), self.out_chan, self.n_pol, 2),
+                                     out_nbit, raw.device)
         n_out = c_int64(0)
-        order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
         fn = self._lib.pfb_filterbank_execute_dada_to_dada if stateful else \
             self._lib.pfb_analysis_execute_dada_to_dada
-        _lib.check(fn(self._h, c_void_p(raw.data_ptr()), int(nbit), int(ndim), order, n_dat,
+        _lib.check(fn(self._h, c_void_p(raw.data_ptr()), int(nbit), int(ndim), _order(lowcbf), n_dat,
                       c_void_p(sec.data_ptr()), int(out_nbit), float(scale), nbytes, byref(n_out),
                       _stream_of(raw, self)))
         return sec[:n_out.value]
@@ -319,8 +381,7 @@ class AnalysisPlan:
         """How the plan's last to-DADA call wrote its section: 'fused' (the analysis kernel
         stored the file's own bytes), 'staged' (the cf32 product packed by a second launch),
         'none' (no such call, or a cf32-output call since) — pfb_analysis_last_dada_output."""
-        m = int(self._lib.pfb_analysis_last_dada_output(self._h))
-        return {_lib.PFB_DADA_OUTPUT_FUSED: "fused", _lib.PFB_DADA_OUTPUT_STAGED: "staged"}.get(m, "none")
+        return _mode_name(self, "pfb_analysis_last_dada_output", _DADA_OUTPUT_NAMES)
 
 
 # ============================================================================ synthesis
@@ -367,15 +428,16 @@ def _resolve_deripple(deripple):
     return bool(getattr(deripple, "apply_deripple")), getattr(deripple, "filter_coeff", None)
 
 
-class SynthesisPlan:
+class SynthesisPlan(_Plan):
     """Device plan of one inverse filter bank (tables, twiddles, scratch, carry-over)."""
+
+    _destroy = "pfb_synthesis_plan_destroy"
 
     def __init__(self, n_chan: int, os_factor, input_fft_length: int, input_overlap: int = None,
                  spans_nyquist: bool = True, combine: int = 1, deripple: bool = False,
                  filter_coeff=None, temporal_taper=None, spectral_taper=None, n_pol: int = 1,
                  device: int = 0):
-        lib = _lib.load()
-        _lib.require_device()
+        super().__init__()
         self.os_factor = as_rational(os_factor)
         self.n_chan = int(n_chan)
         self.input_fft_length = int(input_fft_length)
@@ -403,27 +465,13 @@ class SynthesisPlan:
                                tptr, len(tarr) if filter_coeff is not None else 0,
                                tk, tcp, sk, sco_p, self.n_pol, self.device)
         h = c_void_p()
-        _lib.check(lib.pfb_synthesis_plan_create(byref(d), byref(h)))
+        _lib.check(self._lib.pfb_synthesis_plan_create(byref(d), byref(h)))
         self._h = h
-        self._capture_streams = []  # streams that captured launches of this plan
-        self._lib = lib
         W = (nf * self.os_factor.de) // self.os_factor.nu
         self.output_fft_length = W * self.n_chan
         self.output_overlap = (ov * self.os_factor.de * self.n_chan) // self.os_factor.nu
         self.output_keep = self.output_fft_length - 2 * self.output_overlap
         self.input_keep = nf - 2 * ov
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _close_guard(self)
-            self._lib.pfb_synthesis_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_chunk_blocks(self, blocks: int):
         _lib.check(self._lib.pfb_synthesis_set_chunk_blocks(self._h, int(blocks)))
@@ -443,8 +491,7 @@ class SynthesisPlan:
     def last_stage1_rows(self) -> str:
         """Where the plan's last synthesis launch got its stage-1 rows ('stored',
         'recomputed'; 'none' before any launch) — pfb_synthesis_last_stage1_rows."""
-        m = int(self._lib.pfb_synthesis_last_stage1_rows(self._h))
-        return {_lib.PFB_STAGE1_STORED: "stored", _lib.PFB_STAGE1_RECOMPUTED: "recomputed"}.get(m, "none")
+        return _mode_name(self, "pfb_synthesis_last_stage1_rows", _STAGE1_NAMES)
 
     def output_length(self, n_dat: int) -> int:
         return int(self._lib.pfb_synthesis_output_length(self._h, int(n_dat)))
@@ -475,6 +522,43 @@ class SynthesisPlan:
         ptc = x.transpose(0, 2, 1) if layout == "pfc" else x
         return np.ascontiguousarray(ptc, dtype=np.complex64), False
 
+    def _length_due(self, n_dat: int, sample_offset: int, stateful: bool) -> int:
+        """Samples per polarisation a call of ``n_dat`` rows returns: a stateful call inverts
+        them behind the buffered rows, a stateless one from row ``sample_offset`` (1-based)."""
+        if stateful:
+            return self.output_length(self.buffered_samples + n_dat)
+        return self.output_length(max(n_dat - (int(sample_offset) - 1), 0))
+
+    def _out_buffer(self, out, due: int, device, python_checks_width: bool):
+        """-> (the complex64 (n_pol, width) buffer a cf32-output call writes, the capacity it
+        tells the C ABI): a new buffer of ``due`` samples, or the caller's ``out=``.
+
+        The entries differ on purpose, and tests pin each behaviour — do not unify them.
+        ``execute`` (``python_checks_width``) predates the C ABI's capacity report: it refuses
+        a buffer narrower than ``due`` itself, with ValueError, and passes its width on only
+        when something is due (else ``due`` as it is).  ``execute_view`` and ``execute_dada``
+        leave the width to the C ABI, which answers PFB_ERR_BUFFER_TOO_SMALL before it changes
+        any state, and always pass it on."""
+        t = _torch()
+        if out is None:
+            out = t.empty((self.n_pol, max(due, 0)), dtype=t.complex64, device=device)
+        elif (out.dtype != t.complex64 or out.device != device or not out.is_contiguous()
+              or out.dim() != 2 or out.shape[0] != self.n_pol
+              or (python_checks_width and out.shape[1] < max(due, 0))):
+            width = f">= {max(due, 0)}" if python_checks_width else "n"
+            raise ValueError(f"out must be a contiguous complex64 ({self.n_pol}, {width}) tensor on {device}, "
+                             f"got {tuple(out.shape)} {out.dtype} {out.device}")
+        return out, (due if python_checks_width and due <= 0 else out.shape[1])
+
+    def _run(self, stateful: bool, stream_fn, plan_fn, sample_offset: int, src: tuple, dst: tuple):
+        """One call of a stateful / stateless pair of C ABI entries: the same arguments — the
+        input's, then the output's — with ``sample_offset`` between them for the stateless
+        entry only (the stream object's own is ``set_stream_sample_offset``)."""
+        if stateful:
+            _lib.check(stream_fn(self._h, *src, *dst))
+        else:
+            _lib.check(plan_fn(self._h, *src, int(sample_offset), *dst))
+
     def execute(self, x, sample_offset: int = 1, stateful: bool = False, layout: str = "pfc", out=None):
         """Run the synthesis; returns the (n_pol, n_out) series.  ``out``: an optional
         contiguous complex64 device buffer of at least (n_pol, output length) samples to
@@ -484,21 +568,11 @@ class SynthesisPlan:
             raise ValueError(f"plan built for (n_pol={self.n_pol}, n_chan={self.n_chan}), "
                              f"got {tuple(ptc.shape)} [pol, time, chan]")
         n_dat = ptc.shape[1]
-        if stateful:
-            cap = self.output_length(self.buffered_samples + n_dat)
-        else:
-            cap = self.output_length(max(n_dat - (int(sample_offset) - 1), 0))
+        cap = self._length_due(n_dat, sample_offset, stateful)
         if out is not None and not dev:
             raise ValueError("out= needs device input")
         if dev:
-            t = _torch()
-            if out is None:
-                out = t.empty((self.n_pol, max(cap, 0)), dtype=t.complex64, device=ptc.device)
-            elif (out.dtype != t.complex64 or out.device != ptc.device or not out.is_contiguous()
-                  or out.dim() != 2 or out.shape[0] != self.n_pol or out.shape[1] < max(cap, 0)):
-                raise ValueError(f"out must be a contiguous complex64 ({self.n_pol}, >= {max(cap, 0)}) "
-                                 f"tensor on {ptc.device}, got {tuple(out.shape)} {out.dtype} {out.device}")
-            cap = out.shape[1] if cap > 0 else cap
+            out, cap = self._out_buffer(out, cap, ptc.device, python_checks_width=True)
             src, dst, mem, stream = c_void_p(ptc.data_ptr()), c_void_p(out.data_ptr()), \
                 _lib.PFB_MEM_DEVICE, _stream_of(ptc, self)
         else:
@@ -506,13 +580,8 @@ class SynthesisPlan:
             src, dst, mem, stream = ptc.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p), \
                 _lib.PFB_MEM_HOST, c_void_p(0)
         n_out = c_int64(0)
-        if stateful:
-            _lib.check(self._lib.pfb_inverse_filterbank_execute(
-                self._h, src, n_dat * self.n_chan, n_dat, dst, cap, cap, byref(n_out), mem, stream))
-        else:
-            _lib.check(self._lib.pfb_synthesis_execute(
-                self._h, src, n_dat * self.n_chan, n_dat, int(sample_offset), dst, cap, cap,
-                byref(n_out), mem, stream))
+        self._run(stateful, self._lib.pfb_inverse_filterbank_execute, self._lib.pfb_synthesis_execute,
+                  sample_offset, (src, n_dat * self.n_chan, n_dat), (dst, cap, cap, byref(n_out), mem, stream))
         return out[:, :n_out.value]
 
     def execute_dada(self, raw, nbit: int, ndim: int = 2, lowcbf: bool = False, sample_offset: int = 1,
@@ -523,49 +592,14 @@ class SynthesisPlan:
         unpacked samples crossing HBM where the channel IFFT can read the section itself
         (pfb_synthesis_execute_dada / pfb_inverse_filterbank_execute_dada;
         ``last_dada_input()`` tells).  n_dat is inferred as ``layout.dada_unpack`` does."""
-        t = _torch()
-        if not is_device_array(raw):
-            raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "execute_dada: expects a device tensor")
-        raw = raw.contiguous()
-        if int(nbit) not in (8, 16, 32, 64) or int(ndim) not in (1, 2):
-            n_dat = 0  # (the C ABI rejects the format)
-        else:
-            per = self.n_chan * self.n_pol * int(ndim) * (int(nbit) // 8)
-            n_dat = (raw.numel() * raw.element_size()) // per
-            if lowcbf:
-                n_dat -= n_dat % 32
-        if stateful:
-            cap = self.output_length(self.buffered_samples + n_dat)
-        else:
-            cap = self.output_length(max(n_dat - (int(sample_offset) - 1), 0))
-        if out is None:
-            out = t.empty((self.n_pol, max(cap, 0)), dtype=t.complex64, device=raw.device)
-        elif (out.dtype != t.complex64 or out.device != raw.device or not out.is_contiguous()
-              or out.dim() != 2 or out.shape[0] != self.n_pol):
-            raise ValueError(f"out must be a contiguous complex64 ({self.n_pol}, n) tensor on {raw.device}, "
-                             f"got {tuple(out.shape)} {out.dtype} {out.device}")
-        width = out.shape[1]
-        order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
-        src, dst, stream = c_void_p(raw.data_ptr()), c_void_p(out.data_ptr()), _stream_of(raw, self)
+        raw, n_dat = _section(raw, "execute_dada", self.n_chan * self.n_pol, nbit, ndim, lowcbf)
+        out, width = self._out_buffer(out, self._length_due(n_dat, sample_offset, stateful), raw.device,
+                                      python_checks_width=False)
         n_out = c_int64(0)
-        if stateful:
-            _lib.check(self._lib.pfb_inverse_filterbank_execute_dada(
-                self._h, src, int(nbit), int(ndim), order, n_dat, dst, width, width, byref(n_out), stream))
-        else:
-            _lib.check(self._lib.pfb_synthesis_execute_dada(
-                self._h, src, int(nbit), int(ndim), order, n_dat, int(sample_offset), dst, width, width,
-                byref(n_out), stream))
+        self._run(stateful, self._lib.pfb_inverse_filterbank_execute_dada, self._lib.pfb_synthesis_execute_dada,
+                  sample_offset, (c_void_p(raw.data_ptr()), int(nbit), int(ndim), _order(lowcbf), n_dat),
+                  (c_void_p(out.data_ptr()), width, width, byref(n_out), _stream_of(raw, self)))
         return out[:, :n_out.value]
-
-    def _alloc_section(self, like, n: int, out_nbit: int):
-        """-> (device tensor (n, 1, n_pol, 2) of the DADA sample type, its bytes)."""
-        t = _torch()
-        types = {8: t.int8, 16: t.int16, 32: t.float32, 64: t.float64}
-        if int(out_nbit) not in types:
-            # (the C ABI rejects the format; a byte tensor stands in)
-            return t.empty((0, 1, self.n_pol, 2), dtype=t.int8, device=like.device), 0
-        sec = t.empty((max(n, 0), 1, self.n_pol, 2), dtype=types[int(out_nbit)], device=like.device)
-        return sec, sec.numel() * sec.element_size()
 
     def execute_to_dada(self, chan, out_nbit: int, scale: float = 1.0, sample_offset: int = 1,
                         stateful: bool = False, layout: str = "pfc"):
@@ -582,21 +616,14 @@ class SynthesisPlan:
             raise ValueError(f"plan built for (n_pol={self.n_pol}, n_chan={self.n_chan}), "
                              f"got {tuple(ptc.shape)} [pol, time, chan]")
         n_dat = ptc.shape[1]
-        if stateful:
-            cap = self.output_length(self.buffered_samples + n_dat)
-        else:
-            cap = self.output_length(max(n_dat - (int(sample_offset) - 1), 0))
-        sec, nbytes = self._alloc_section(ptc, cap, out_nbit)
-        src, dst, stream = c_void_p(ptc.data_ptr()), c_void_p(sec.data_ptr()), _stream_of(ptc, self)
+        sec, nbytes = _alloc_section((self._length_due(n_dat, sample_offset, stateful), 1, self.n_pol, 2),
+                                     out_nbit, ptc.device)
         n_out = c_int64(0)
-        if stateful:
-            _lib.check(self._lib.pfb_inverse_filterbank_execute_to_dada(
-                self._h, src, n_dat * self.n_chan, n_dat, dst, int(out_nbit), float(scale), nbytes,
-                byref(n_out), stream))
-        else:
-            _lib.check(self._lib.pfb_synthesis_execute_to_dada(
-                self._h, src, n_dat * self.n_chan, n_dat, int(sample_offset), dst, int(out_nbit),
-                float(scale), nbytes, byref(n_out), stream))
+        self._run(stateful, self._lib.pfb_inverse_filterbank_execute_to_dada,
+                  self._lib.pfb_synthesis_execute_to_dada, sample_offset,
+                  (c_void_p(ptc.data_ptr()), n_dat * self.n_chan, n_dat),
+                  (c_void_p(sec.data_ptr()), int(out_nbit), float(scale), nbytes, byref(n_out),
+                   _stream_of(ptc, self)))
         return sec[:n_out.value]
 
     def execute_dada_to_dada(self, raw, nbit: int, out_nbit: int, scale: float = 1.0, ndim: int = 2,
@@ -605,40 +632,22 @@ class SynthesisPlan:
         bytes in, file bytes out (pfb_synthesis_execute_dada_to_dada /
         pfb_inverse_filterbank_execute_dada_to_dada); ``last_dada_input()`` and
         ``last_dada_output()`` tell which sides the kernels read and wrote in place."""
-        if not is_device_array(raw):
-            raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "execute_dada_to_dada: expects a device tensor")
-        raw = raw.contiguous()
-        if int(nbit) not in (8, 16, 32, 64) or int(ndim) not in (1, 2):
-            n_dat = 0  # (the C ABI rejects the format)
-        else:
-            per = self.n_chan * self.n_pol * int(ndim) * (int(nbit) // 8)
-            n_dat = (raw.numel() * raw.element_size()) // per
-            if lowcbf:
-                n_dat -= n_dat % 32
-        if stateful:
-            cap = self.output_length(self.buffered_samples + n_dat)
-        else:
-            cap = self.output_length(max(n_dat - (int(sample_offset) - 1), 0))
-        sec, nbytes = self._alloc_section(raw, cap, out_nbit)
-        order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
-        src, dst, stream = c_void_p(raw.data_ptr()), c_void_p(sec.data_ptr()), _stream_of(raw, self)
+        raw, n_dat = _section(raw, "execute_dada_to_dada", self.n_chan * self.n_pol, nbit, ndim, lowcbf)
+        sec, nbytes = _alloc_section((self._length_due(n_dat, sample_offset, stateful), 1, self.n_pol, 2),
+                                     out_nbit, raw.device)
         n_out = c_int64(0)
-        if stateful:
-            _lib.check(self._lib.pfb_inverse_filterbank_execute_dada_to_dada(
-                self._h, src, int(nbit), int(ndim), order, n_dat, dst, int(out_nbit), float(scale), nbytes,
-                byref(n_out), stream))
-        else:
-            _lib.check(self._lib.pfb_synthesis_execute_dada_to_dada(
-                self._h, src, int(nbit), int(ndim), order, n_dat, int(sample_offset), dst, int(out_nbit),
-                float(scale), nbytes, byref(n_out), stream))
+        self._run(stateful, self._lib.pfb_inverse_filterbank_execute_dada_to_dada,
+                  self._lib.pfb_synthesis_execute_dada_to_dada, sample_offset,
+                  (c_void_p(raw.data_ptr()), int(nbit), int(ndim), _order(lowcbf), n_dat),
+                  (c_void_p(sec.data_ptr()), int(out_nbit), float(scale), nbytes, byref(n_out),
+                   _stream_of(raw, self)))
         return sec[:n_out.value]
 
     def last_dada_output(self) -> str:
         """How the plan's last to-DADA call wrote its section: 'fused' (the synthesis kernel
         stored the file's own bytes), 'staged' (the cf32 series packed by a second launch),
         'none' (no such call, or a cf32-output call since) — pfb_synthesis_last_dada_output."""
-        m = int(self._lib.pfb_synthesis_last_dada_output(self._h))
-        return {_lib.PFB_DADA_OUTPUT_FUSED: "fused", _lib.PFB_DADA_OUTPUT_STAGED: "staged"}.get(m, "none")
+        return _mode_name(self, "pfb_synthesis_last_dada_output", _DADA_OUTPUT_NAMES)
 
     def execute_view(self, x, sample_offset: int = 1, stateful: bool = False, out=None):
         """The synthesis of a strided view: ``x`` is any complex64 device tensor view shaped
@@ -655,48 +664,51 @@ class SynthesisPlan:
             raise ValueError(f"plan built for (n_pol={self.n_pol}, n_chan={self.n_chan}), "
                              f"got {tuple(x.shape)} [pol, time, chan]")
         n_dat = int(x.shape[1])
-        if stateful:
-            cap = self.output_length(self.buffered_samples + n_dat)
-        else:
-            cap = self.output_length(max(n_dat - (int(sample_offset) - 1), 0))
-        if out is None:
-            out = t.empty((self.n_pol, max(cap, 0)), dtype=t.complex64, device=x.device)
-        elif (out.dtype != t.complex64 or out.device != x.device or not out.is_contiguous()
-              or out.dim() != 2 or out.shape[0] != self.n_pol):
-            raise ValueError(f"out must be a contiguous complex64 ({self.n_pol}, n) tensor on {x.device}, "
-                             f"got {tuple(out.shape)} {out.dtype} {out.device}")
-        width = out.shape[1]
+        out, width = self._out_buffer(out, self._length_due(n_dat, sample_offset, stateful), x.device,
+                                      python_checks_width=False)
         # elements available from the view's first element to the end of its storage
         in_cap = x.untyped_storage().nbytes() // x.element_size() - x.storage_offset()
         ps, rs, cs = (int(v) for v in x.stride())
-        src, dst, stream = c_void_p(x.data_ptr()), c_void_p(out.data_ptr()), _stream_of(x, self)
         n_out = c_int64(0)
-        if stateful:
-            _lib.check(self._lib.pfb_inverse_filterbank_execute_strided(
-                self._h, src, ps, rs, cs, in_cap, n_dat, dst, width, width, byref(n_out), stream))
-        else:
-            _lib.check(self._lib.pfb_synthesis_execute_strided(
-                self._h, src, ps, rs, cs, in_cap, n_dat, int(sample_offset), dst, width, width,
-                byref(n_out), stream))
+        self._run(stateful, self._lib.pfb_inverse_filterbank_execute_strided,
+                  self._lib.pfb_synthesis_execute_strided, sample_offset,
+                  (c_void_p(x.data_ptr()), ps, rs, cs, in_cap, n_dat),
+                  (c_void_p(out.data_ptr()), width, width, byref(n_out), _stream_of(x, self)))
         return out[:, :n_out.value]
 
     def last_strided_input(self) -> str:
         """How the plan's last strided call read its rows: 'in_place' (the channel IFFT
         loaded through the layout), 'staged' (copied to a packed buffer first), 'none' (no
         strided call, or a packed or DADA call since) — pfb_synthesis_last_strided_input."""
-        m = int(self._lib.pfb_synthesis_last_strided_input(self._h))
-        return {_lib.PFB_STRIDED_INPUT_IN_PLACE: "in_place",
-                _lib.PFB_STRIDED_INPUT_STAGED: "staged"}.get(m, "none")
+        return _mode_name(self, "pfb_synthesis_last_strided_input", _STRIDED_INPUT_NAMES)
 
     def last_dada_input(self) -> str:
         """How the plan's last DADA call read its section: 'fused' (the channel IFFT read
         the file's own bytes), 'staged' (unpacked first), 'none' (no DADA call, or a cf32
         call since) — pfb_synthesis_last_dada_input."""
-        m = int(self._lib.pfb_synthesis_last_dada_input(self._h))
-        return {_lib.PFB_DADA_INPUT_FUSED: "fused", _lib.PFB_DADA_INPUT_STAGED: "staged"}.get(m, "none")
+        return _mode_name(self, "pfb_synthesis_last_dada_input", _DADA_INPUT_NAMES)
 
 
 # ============================================================================ round trip
+def _rt_lengths(analysis, synthesis, n_dat: int, sample_offset: int, n_pol: int = None):
+    """-> (K, n_out): the rows the analysis of ``n_dat`` samples makes and the samples the
+    synthesis returns from row ``sample_offset`` of them.  ``n_pol``: the polarisations of the
+    call's input, which both plans must be built for (the synthesis halves have no input and
+    leave the pair's agreement to the C ABI)."""
+    if n_pol is not None and not (analysis.n_pol == synthesis.n_pol == n_pol):
+        raise ValueError(f"plans built for n_pol={analysis.n_pol}/{synthesis.n_pol}, input of n_pol={n_pol}")
+    K = analysis.output_length(int(n_dat))
+    return K, synthesis._length_due(K, sample_offset, False)
+
+
+def _release_rt_input(synthesis, device):
+    """After a round trip's synthesis half has been enqueued on ``device``'s current stream: with
+    recomputed stage-1 rows that work read the input ``roundtrip_analysis`` kept."""
+    if synthesis._rt_input is not None:
+        _keep_alive(synthesis, synthesis._rt_input, device)
+        synthesis._rt_input = None
+
+
 def roundtrip(analysis: AnalysisPlan, synthesis: SynthesisPlan, x, sample_offset: int = 1,
               chan=None, out=None):
     """Analysis -> synthesis of ``x`` (device tensor, (n_pol, n_dat) or (n_pol, 1, n_dat))
@@ -712,20 +724,16 @@ def roundtrip(analysis: AnalysisPlan, synthesis: SynthesisPlan, x, sample_offset
     x, dev = analysis._prep_in(x)
     if not dev:
         raise ValueError("roundtrip() takes device tensors (use the separate calls for host arrays)")
-    t = _torch()
     n_pol, n_dat = x.shape
-    if n_pol != analysis.n_pol or n_pol != synthesis.n_pol:
-        raise ValueError(f"plans built for n_pol={analysis.n_pol}/{synthesis.n_pol}, got {n_pol}")
-    K = analysis.output_length(n_dat)
-    n_out = synthesis.output_length(max(K - (int(sample_offset) - 1), 0))
-    if chan is None:
-        chan = t.empty((n_pol, max(K, 0), analysis.n_chan), dtype=t.complex64, device=x.device)
+    K, n_out = _rt_lengths(analysis, synthesis, n_dat, sample_offset, n_pol)
+    if chan is None:  # (x is complex64 on its device: _prep_in)
+        chan = x.new_empty((n_pol, max(K, 0), analysis.n_chan))
     if out is None:
-        out = t.empty((n_pol, max(n_out, 0)), dtype=t.complex64, device=x.device)
+        out = x.new_empty((n_pol, max(n_out, 0)))
     if tuple(chan.shape) != (n_pol, K, analysis.n_chan) or tuple(out.shape) != (n_pol, n_out):
         raise ValueError("preallocated chan/out have the wrong shape")
     kr, no = c_int64(0), c_int64(0)
-    _lib.check(_lib.load().pfb_roundtrip_execute(
+    _lib.check(analysis._lib.pfb_roundtrip_execute(
         analysis._h, synthesis._h, c_void_p(x.data_ptr()), n_dat, n_dat,
         c_void_p(chan.data_ptr()), K * analysis.n_chan, K, byref(kr), int(sample_offset),
         c_void_p(out.data_ptr()), max(n_out, 1), n_out, byref(no), _stream_of(x, analysis, synthesis)))
@@ -743,17 +751,14 @@ def roundtrip_analysis(analysis: AnalysisPlan, synthesis: SynthesisPlan, x, samp
     x, dev = analysis._prep_in(x)
     if not dev:
         raise ValueError("roundtrip_analysis() takes device tensors")
-    t = _torch()
     n_pol, n_dat = x.shape
-    if n_pol != analysis.n_pol or n_pol != synthesis.n_pol:
-        raise ValueError(f"plans built for n_pol={analysis.n_pol}/{synthesis.n_pol}, got {n_pol}")
-    K = analysis.output_length(n_dat)
+    K, _ = _rt_lengths(analysis, synthesis, n_dat, sample_offset, n_pol)
     if chan is None:
-        chan = t.empty((n_pol, max(K, 0), analysis.n_chan), dtype=t.complex64, device=x.device)
+        chan = x.new_empty((n_pol, max(K, 0), analysis.n_chan))
     if tuple(chan.shape) != (n_pol, K, analysis.n_chan):
         raise ValueError("preallocated chan has the wrong shape")
     kr = c_int64(0)
-    _lib.check(_lib.load().pfb_roundtrip_analysis_execute(
+    _lib.check(analysis._lib.pfb_roundtrip_analysis_execute(
         analysis._h, synthesis._h, c_void_p(x.data_ptr()), n_dat, n_dat,
         c_void_p(chan.data_ptr()), K * analysis.n_chan, K, byref(kr), int(sample_offset),
         _stream_of(x, analysis, synthesis)))
@@ -772,8 +777,7 @@ def roundtrip_synthesis(analysis: AnalysisPlan, synthesis: SynthesisPlan, n_dat:
     current stream of ``out``'s device (or ``device``)."""
     t = _torch()
     n_pol = synthesis.n_pol
-    K = analysis.output_length(int(n_dat))
-    n_out = synthesis.output_length(max(K - (int(sample_offset) - 1), 0))
+    _, n_out = _rt_lengths(analysis, synthesis, n_dat, sample_offset)
     if out is None:
         dv = t.device("cuda", synthesis.device if device is None else device)
         out = t.empty((n_pol, max(n_out, 0)), dtype=t.complex64, device=dv)
@@ -781,53 +785,11 @@ def roundtrip_synthesis(analysis: AnalysisPlan, synthesis: SynthesisPlan, n_dat:
         raise ValueError("preallocated out has the wrong shape")
     no = c_int64(0)
     stream = _stream_of(out, analysis, synthesis)
-    _lib.check(_lib.load().pfb_roundtrip_synthesis_execute(
+    _lib.check(analysis._lib.pfb_roundtrip_synthesis_execute(
         analysis._h, synthesis._h, int(n_dat), int(sample_offset), c_void_p(out.data_ptr()),
         max(n_out, 1), n_out, byref(no), stream))
-    xin = getattr(synthesis, "_rt_input", None)
-    if xin is not None:
-        # the analysis half's input (recomputed rows read it here): its memory may be reused
-        # only after the work just enqueued on this stream has finished
-        if not t.cuda.is_current_stream_capturing():
-            xin.record_stream(t.cuda.current_stream(out.device))
-        else:
-            # a captured launch holds the input's address for every replay: keep the tensor
-            # alive as long as the plan (one entry per address, so recaptures do not grow it)
-            held = synthesis.__dict__.setdefault("_graph_inputs", {})
-            held[xin.data_ptr()] = xin
-        synthesis._rt_input = None
+    _release_rt_input(synthesis, out.device)
     return out
-
-
-_SECTION_TYPES = {8: "int8", 16: "int16", 32: "float32", 64: "float64"}
-
-
-def _section_samples(raw, n_pol: int, nbit: int, ndim: int, lowcbf: bool) -> int:
-    """Samples per polarisation a single-channel section tensor holds (0: a format the C ABI
-    rejects)."""
-    if int(nbit) not in (8, 16, 32, 64) or int(ndim) not in (1, 2):
-        return 0
-    n_dat = (raw.numel() * raw.element_size()) // (n_pol * int(ndim) * (int(nbit) // 8))
-    return n_dat - n_dat % 32 if lowcbf else n_dat
-
-
-def _alloc_rt_section(shape, nbit: int, device):
-    """-> (device tensor of the DADA sample type, its bytes); a format the C ABI rejects gets
-    an empty byte tensor to stand in."""
-    t = _torch()
-    if int(nbit) not in _SECTION_TYPES:
-        return t.empty((0,) + tuple(shape[1:]), dtype=t.int8, device=device), 0
-    sec = t.empty(tuple(max(int(v), 0) for v in shape), dtype=getattr(t, _SECTION_TYPES[int(nbit)]),
-                  device=device)
-    return sec, sec.numel() * sec.element_size()
-
-
-def _hold_captured_section(synthesis, raw):
-    """A captured launch holds the section's address for every replay, and ``raw`` may be the
-    temporary ``.contiguous()`` made: keep it alive as long as the plan (roundtrip_synthesis's
-    rule for captured inputs; one entry per address)."""
-    if _torch().cuda.is_current_stream_capturing():
-        synthesis.__dict__.setdefault("_graph_inputs", {})[raw.data_ptr()] = raw
 
 
 def roundtrip_dada(analysis: AnalysisPlan, synthesis: SynthesisPlan, raw, nbit: int, out_nbit: int,
@@ -841,25 +803,18 @@ def roundtrip_dada(analysis: AnalysisPlan, synthesis: SynthesisPlan, raw, nbit: 
     ``layout.dada_pack`` of both results; ``analysis.last_dada_input()``,
     ``analysis.last_dada_output()`` and ``synthesis.last_dada_output()`` tell whether the
     kernels read and wrote the sections themselves."""
-    if not is_device_array(raw):
-        raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "roundtrip_dada: expects a device tensor")
-    if analysis.n_pol != synthesis.n_pol:
-        raise ValueError(f"plans built for n_pol={analysis.n_pol}/{synthesis.n_pol}")
-    raw = raw.contiguous()
     n_pol = analysis.n_pol
-    n_dat = _section_samples(raw, n_pol, nbit, ndim, lowcbf)
-    K = analysis.output_length(n_dat)
-    n_out = synthesis.output_length(max(K - (int(sample_offset) - 1), 0))
-    chan, chan_bytes = _alloc_rt_section((K, analysis.n_chan, n_pol, 2), 32, raw.device)
-    out, out_bytes = _alloc_rt_section((n_out, 1, n_pol, 2), out_nbit, raw.device)
-    order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
+    raw, n_dat = _section(raw, "roundtrip_dada", n_pol, nbit, ndim, lowcbf)
+    K, n_out = _rt_lengths(analysis, synthesis, n_dat, sample_offset, n_pol)
+    chan, chan_bytes = _alloc_section((K, analysis.n_chan, n_pol, 2), 32, raw.device)
+    out, out_bytes = _alloc_section((n_out, 1, n_pol, 2), out_nbit, raw.device)
     kr, no = c_int64(0), c_int64(0)
-    _lib.check(_lib.load().pfb_roundtrip_execute_dada_to_dada(
-        analysis._h, synthesis._h, c_void_p(raw.data_ptr()), int(nbit), int(ndim), order, n_dat,
+    _lib.check(analysis._lib.pfb_roundtrip_execute_dada_to_dada(
+        analysis._h, synthesis._h, c_void_p(raw.data_ptr()), int(nbit), int(ndim), _order(lowcbf), n_dat,
         c_void_p(chan.data_ptr()), chan_bytes, byref(kr), int(sample_offset),
         c_void_p(out.data_ptr()), int(out_nbit), float(scale), out_bytes, byref(no),
         _stream_of(raw, analysis, synthesis)))
-    _hold_captured_section(synthesis, raw)
+    _keep_alive(synthesis, raw, raw.device)
     return chan[:kr.value], out[:no.value]
 
 
@@ -870,22 +825,16 @@ def roundtrip_analysis_dada(analysis: AnalysisPlan, synthesis: SynthesisPlan, ra
     for ``roundtrip_synthesis_to_dada`` (or ``roundtrip_synthesis``).  The rows are always
     stored, so the synthesis half never comes back to ``raw``.  ``PfbError`` (unsupported)
     when the plans take the chunked pipeline."""
-    if not is_device_array(raw):
-        raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "roundtrip_analysis_dada: expects a device tensor")
-    if analysis.n_pol != synthesis.n_pol:
-        raise ValueError(f"plans built for n_pol={analysis.n_pol}/{synthesis.n_pol}")
-    raw = raw.contiguous()
     n_pol = analysis.n_pol
-    n_dat = _section_samples(raw, n_pol, nbit, ndim, lowcbf)
-    K = analysis.output_length(n_dat)
-    chan, chan_bytes = _alloc_rt_section((K, analysis.n_chan, n_pol, 2), 32, raw.device)
-    order = _lib.PFB_DADA_LOWCBF if lowcbf else _lib.PFB_DADA_TFP
+    raw, n_dat = _section(raw, "roundtrip_analysis_dada", n_pol, nbit, ndim, lowcbf)
+    K, _ = _rt_lengths(analysis, synthesis, n_dat, sample_offset, n_pol)
+    chan, chan_bytes = _alloc_section((K, analysis.n_chan, n_pol, 2), 32, raw.device)
     kr = c_int64(0)
-    _lib.check(_lib.load().pfb_roundtrip_analysis_execute_dada(
-        analysis._h, synthesis._h, c_void_p(raw.data_ptr()), int(nbit), int(ndim), order, n_dat,
+    _lib.check(analysis._lib.pfb_roundtrip_analysis_execute_dada(
+        analysis._h, synthesis._h, c_void_p(raw.data_ptr()), int(nbit), int(ndim), _order(lowcbf), n_dat,
         c_void_p(chan.data_ptr()), chan_bytes, byref(kr), int(sample_offset),
         _stream_of(raw, analysis, synthesis)))
-    _hold_captured_section(synthesis, raw)
+    _keep_alive(synthesis, raw, raw.device)
     return chan[:kr.value]
 
 
@@ -896,25 +845,15 @@ def roundtrip_synthesis_to_dada(analysis: AnalysisPlan, synthesis: SynthesisPlan
     ``sample_offset``: returns the output section, equal to ``roundtrip_dada``'s bit for bit.
     Runs on the current stream of ``device`` (default: the synthesis plan's)."""
     t = _torch()
-    n_pol = synthesis.n_pol
-    K = analysis.output_length(int(n_dat))
-    n_out = synthesis.output_length(max(K - (int(sample_offset) - 1), 0))
+    _, n_out = _rt_lengths(analysis, synthesis, n_dat, sample_offset)
     dv = t.device("cuda", synthesis.device if device is None else device)
-    out, out_bytes = _alloc_rt_section((n_out, 1, n_pol, 2), out_nbit, dv)
+    out, out_bytes = _alloc_section((n_out, 1, synthesis.n_pol, 2), out_nbit, dv)
     no = c_int64(0)
     stream = _stream_of(out, analysis, synthesis)
-    _lib.check(_lib.load().pfb_roundtrip_synthesis_execute_to_dada(
+    _lib.check(analysis._lib.pfb_roundtrip_synthesis_execute_to_dada(
         analysis._h, synthesis._h, int(n_dat), int(sample_offset), c_void_p(out.data_ptr()),
         int(out_nbit), float(scale), out_bytes, byref(no), stream))
-    xin = getattr(synthesis, "_rt_input", None)
-    if xin is not None:
-        # (roundtrip_synthesis's rule for the input of a cf32 analysis half with recomputed rows)
-        if not t.cuda.is_current_stream_capturing():
-            xin.record_stream(t.cuda.current_stream(out.device))
-        else:
-            held = synthesis.__dict__.setdefault("_graph_inputs", {})
-            held[xin.data_ptr()] = xin
-        synthesis._rt_input = None
+    _release_rt_input(synthesis, out.device)  # (a cf32 analysis half with recomputed rows)
     return out[:no.value]
 
 
@@ -994,27 +933,33 @@ def _npol(x) -> int:
 
 
 # ============================================================================ functions
-def polyphase_analysis(in_, filt, block, os_factor, verbose_=0):
-    """polyphase_analysis.m:1-129 (Bunton).  Returns (n_pol, block, nblocks) complex64."""
-    plan = analysis_plan(filt, block, os_factor, "polyphase_analysis", _npol(in_),
-                         _device_of(in_))
-    return _pfc_view(plan.execute(in_))
+def _analysis_function(variant: str, doc: str, fixed: tuple = None):
+    """The Matlab-shaped function of analysis ``variant``.  ``fixed``: the (block, os_factor)
+    the variant always has; they become the arguments' defaults, and what is passed is ignored."""
+    def fn(in_, filt, block, os_factor, verbose_=0):
+        if fixed:
+            block, os_factor = fixed
+        plan = analysis_plan(filt, block, os_factor, variant, _npol(in_), _device_of(in_))
+        return _pfc_view(plan.execute(in_))
+    if fixed:
+        fn.__defaults__ = fixed + (0,)
+    fn.__name__ = fn.__qualname__ = variant
+    fn.__doc__ = doc
+    return fn
 
 
-def polyphase_analysis_padded(in_, filt, block, os_factor, verbose_=0):
-    """polyphase_analysis_padded.m:1-161 (commutator).  Returns (n_pol, block, nblocks)."""
-    plan = analysis_plan(filt, block, os_factor, "polyphase_analysis_padded", _npol(in_),
-                         _device_of(in_))
-    return _pfc_view(plan.execute(in_))
-
-
-def polyphase_analysis_lowcbf(in_, filt, block=256, os_factor="4/3", verbose_=0):
+polyphase_analysis = _analysis_function(
+    "polyphase_analysis",
+    """polyphase_analysis.m:1-129 (Bunton).  Returns (n_pol, block, nblocks) complex64.""")
+polyphase_analysis_padded = _analysis_function(
+    "polyphase_analysis_padded",
+    """polyphase_analysis_padded.m:1-161 (commutator).  Returns (n_pol, block, nblocks).""")
+polyphase_analysis_lowcbf = _analysis_function(
+    "polyphase_analysis_lowcbf",
     """polyphase_analysis_lowcbf.m:1-49 (SKA-Low CBF PST filterbank, PSTFilterbank.m).
     Returns (n_pol, 216, nblocks).  The wrapper's ``persistent do_padding`` (1536 zeros
-    before the first call's data only) lives in the cached plan of these taps."""
-    plan = analysis_plan(filt, 256, "4/3", "polyphase_analysis_lowcbf", _npol(in_),
-                         _device_of(in_))
-    return _pfc_view(plan.execute(in_))
+    before the first call's data only) lives in the cached plan of these taps.""",
+    fixed=(256, "4/3"))
 
 
 def polyphase_synthesis(in_, input_fully_spans_Nyquist_zone, input_fft_length, os_factor,

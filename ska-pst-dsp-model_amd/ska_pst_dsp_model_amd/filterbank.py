@@ -9,13 +9,12 @@ the device plan (``pfb_filterbank_execute`` / ``pfb_inverse_filterbank_execute``
 from __future__ import annotations
 
 import abc
-from types import SimpleNamespace
 
 import numpy as np
 
-from . import _lib, layout
+from . import layout
 from .config import as_rational
-from .core import AnalysisPlan, SynthesisPlan, is_device_array
+from .core import AnalysisPlan, SynthesisPlan, _npol, _pfc_view, is_device_array
 from .firio import read_fir_filter_coeff
 from .window import PFBWindow, identity_taper
 
@@ -50,10 +49,6 @@ class DeChannelizer(abc.ABC):
     @abc.abstractmethod
     def execute(self, input):  # noqa: A002
         ...
-
-
-def _npol(x):
-    return 1 if len(tuple(x.shape)) == 1 else int(tuple(x.shape)[0])
 
 
 def _to_device(x, device):
@@ -121,8 +116,7 @@ class FilterBank(Channelizer):
         out = plan.execute(x, stateful=True)  # (n_pol, T_out, n_chan)
         if self.rndOutput:
             out = _quantize(out, self.rmsOutput, self.device)
-        view = out.transpose(1, 2) if is_device_array(out) else out.transpose(0, 2, 1)
-        return self, view
+        return self, _pfc_view(out)
 
     def execute_dada(self, raw, nbit: int, ndim: int = 2, n_pol: int = 1):
         """``execute`` of the next chunk as the file holds it: ``raw`` is a device tensor of
@@ -241,16 +235,20 @@ class InverseFilterBank(DeChannelizer):
     def buffered_samples(self) -> int:
         return 0 if self._plan is None else self._plan.buffered_samples
 
+    def _stream_plan(self, n_pol, n_chan):
+        """Every call's preamble: the plan of this shape, told the object's ``sample_offset``
+        — polyphase_synthesis(..., obj.sample_offset+1, ...) on every call (:92-96)."""
+        if int(self.sample_offset) < 0:
+            raise ValueError("sample_offset is 0-based (>= 0)")
+        plan = self._ensure_plan(n_pol, n_chan)
+        plan.set_stream_sample_offset(int(self.sample_offset))
+        return plan
+
     def execute(self, input):  # noqa: A002
         shape = tuple(input.shape)
         if not is_device_array(input) and not np.iscomplexobj(np.asarray(input)):
             raise ValueError("polyphase_synthesis input data are real-valued!")
-        if int(self.sample_offset) < 0:
-            raise ValueError("sample_offset is 0-based (>= 0)")
-        plan = self._ensure_plan(shape[0], shape[1])
-        # polyphase_synthesis(..., obj.sample_offset+1, ...) on every call (:92-96)
-        plan.set_stream_sample_offset(int(self.sample_offset))
-        out = plan.execute(input, stateful=True)
+        out = self._stream_plan(shape[0], shape[1]).execute(input, stateful=True)
         return self, out[:, None, :]
 
     def execute_view(self, view):
@@ -259,10 +257,7 @@ class InverseFilterBank(DeChannelizer):
         coarse-channel slices of a two-stage product, a channel window, channel-major
         rows).  Same output and carry as ``execute(view.transpose(1, 2))``, bit for bit,
         with no packed copy of the view (``SynthesisPlan.execute_view``)."""
-        if int(self.sample_offset) < 0:
-            raise ValueError("sample_offset is 0-based (>= 0)")
-        plan = self._ensure_plan(int(view.shape[0]), int(view.shape[2]))
-        plan.set_stream_sample_offset(int(self.sample_offset))
+        plan = self._stream_plan(int(view.shape[0]), int(view.shape[2]))
         out = plan.execute_view(view, stateful=True)
         return self, out[:, None, :]
 
@@ -270,10 +265,7 @@ class InverseFilterBank(DeChannelizer):
         """``execute`` of the next chunk as the file holds it: ``raw`` is a device tensor of
         the DADA section's bytes (``DADARead.generate_raw``), ``nchan`` channels x ``n_pol``
         polarisations.  Same output and carry as ``execute(DADARead.generate(...))``."""
-        if int(self.sample_offset) < 0:
-            raise ValueError("sample_offset is 0-based (>= 0)")
-        plan = self._ensure_plan(int(n_pol), int(self.nchan))
-        plan.set_stream_sample_offset(int(self.sample_offset))
+        plan = self._stream_plan(int(n_pol), int(self.nchan))
         out = plan.execute_dada(raw, nbit, ndim=ndim, lowcbf=lowcbf, stateful=True)
         return self, out[:, None, :]
 
@@ -303,10 +295,7 @@ class InverseFilterBank(DeChannelizer):
             _, out = self.execute(input)
             return self, self._pack_out(out, nbit, scale)
         shape = tuple(input.shape)
-        if int(self.sample_offset) < 0:
-            raise ValueError("sample_offset is 0-based (>= 0)")
-        plan = self._ensure_plan(shape[0], shape[1])
-        plan.set_stream_sample_offset(int(self.sample_offset))
+        plan = self._stream_plan(shape[0], shape[1])
         return self, plan.execute_to_dada(input, nbit, scale=scale, stateful=True)
 
     def execute_dada_to_dada(self, raw, in_nbit: int, out_nbit: int, scale: float = 1.0, ndim: int = 2,
@@ -316,10 +305,7 @@ class InverseFilterBank(DeChannelizer):
         if self._quantised_output():
             _, out = self.execute_dada(raw, in_nbit, ndim=ndim, lowcbf=lowcbf, n_pol=n_pol)
             return self, self._pack_out(out, out_nbit, scale)
-        if int(self.sample_offset) < 0:
-            raise ValueError("sample_offset is 0-based (>= 0)")
-        plan = self._ensure_plan(int(n_pol), int(self.nchan))
-        plan.set_stream_sample_offset(int(self.sample_offset))
+        plan = self._stream_plan(int(n_pol), int(self.nchan))
         return self, plan.execute_dada_to_dada(raw, in_nbit, out_nbit, scale=scale, ndim=ndim, lowcbf=lowcbf,
                                                stateful=True)
 

@@ -193,7 +193,7 @@ class SynthesisShape(namedtuple("SynthesisShape", "N nu de Nf Ov sample_offset")
 
     @property
     def Lkeep(self):
-        """Output samples per block: W N - 2 Lov (ska_pst_dsp_model_amd/core.py:345-348)."""
+        """Output samples per block: W N - 2 Lov (SynthesisPlan.__init__)."""
         W = (self.Nf * self.de) // self.nu
         return W * self.N - 2 * ((self.Ov * self.de * self.N) // self.nu)
 
