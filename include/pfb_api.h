@@ -670,6 +670,46 @@ pfb_status pfb_quantize(const pfb_cf32* in, int64_t in_pol_stride, int64_t n, in
                         double rms, pfb_cf32* out, int64_t out_pol_stride, double* scale,
                         void* stream);
 
+/* ---------------------------------------------------------------- verification */
+/* The reference's verification loop (current_performance.m) on the device: per test vector
+ * generate -> round trip -> score, with nothing but a few doubles per vector crossing to the
+ * host.  Device pointers, strides in complex elements, n_vec <= 65535; every argument check
+ * runs before any device call: n <= 0, n_vec <= 0, a stride below n, a null buffer, a series
+ * not aligned to 8 bytes, domain < 0, an unknown kind or dtype and a non-finite scale or
+ * parameter are PFB_ERR_INVALID_ARG.  The scores accumulate in double and are deterministic
+ * (per-workgroup partials combined in a fixed order: the same data give the same bits).  They
+ * use the current device's scratch, so the caller makes the series' device current. */
+typedef enum pfb_testvec_kind { PFB_TESTVEC_IMPULSE = 0, PFB_TESTVEC_SINUSOID = 1 } pfb_testvec_kind;
+
+/* out[v*out_stride + t], t < n, for v < n_vec.  kind[v], param[4*v .. 4*v+3] are HOST arrays.
+ * IMPULSE  (time_domain_impulse.m:13-24): param = {offset (1-based), width, -, -}: ones at
+ *          offset-1 .. offset-2+width clipped to [0, n), zeros elsewhere.
+ * SINUSOID (complex_sinusoid.m:16-31):   param = {frequency, phase, bin_offset, -}:
+ *          ph = ((2*pi*(frequency+bin_offset))/n)*t + phase evaluated in double in exactly this
+ *          order, out = (float)cos(ph), (float)sin(ph).
+ * Asynchronous on stream.  Writes nothing outside [0, n) of each row. */
+pfb_status pfb_testvec_generate(const int32_t* kind, const double* param, int32_t n_vec, int64_t n,
+                                pfb_cf32* out, int64_t out_stride, void* stream);
+
+/* ErrorAnalysis.m:5-52 + DomainPerformance.m:67-100 + TestImpulse.m:46-73 on n_vec series.
+ * p[t] = scale * (re^2 + im^2) in double; dtype 0 = complex float32, 1 = complex float64.
+ * result (HOST, n_vec x 6 doubles):
+ *  [0] k = first index of max p   [1] p[k]
+ *  [2] max and [3] sum of p with indices max(k-domain,0) .. min(k+domain,n-1) zeroed
+ *      (the unmasked terms summed directly, not a total minus the window)
+ *  [4] p[e] and [5] max of p outside max(e-1,0) .. e+1, where e = expected[v];
+ *      both -1 when expected is null, e < 0 or e >= n.
+ * expected: HOST array or null.  Synchronises the stream. */
+pfb_status pfb_purity_score_spurious(const void* a, int32_t dtype, int64_t stride, int64_t n,
+                                     int32_t n_vec, double scale, int32_t domain,
+                                     const int64_t* expected, double* result, void* stream);
+
+/* DomainPerformance.m:7-64 (correct_phase 0): d[t] = |a[t]-b[t]|^2 in double;
+ * result (HOST, n_vec x 2): max d, sum d.  Synchronises the stream. */
+pfb_status pfb_purity_score_difference(const pfb_cf32* a, int64_t a_stride, const pfb_cf32* b,
+                                       int64_t b_stride, int64_t n, int32_t n_vec, double* result,
+                                       void* stream);
+
 /* ---------------------------------------------------------------- utilities */
 const char* pfb_last_error(void);
 int32_t pfb_api_version(void);

@@ -3,7 +3,7 @@ tones + the sgcht.m frequency comb and square wave; sub-config 'mid') on the HIP
 scored as the reference scores it (verify.score_vector).  One JSON record per vector,
 then a summary line.
 
-    python scripts/purity_sweep.py [--npoints 300] [--batch 16]
+    python scripts/purity_sweep.py [--npoints 300] [--batch 16] [--scoring {host,device}]
     python -m torch.distributed.run --nproc-per-node 8 scripts/purity_sweep.py ...
 
 Under a launcher the vectors are dealt round-robin over the ranks (one GPU each, no
@@ -66,6 +66,11 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--max-vectors", type=int, default=0)
     ap.add_argument("--out-dir", default=os.path.join(REPO, "gpurun_out", "purity"))
+    ap.add_argument("--scoring", choices=("host", "device"), default="device",
+                    help="device (default: the measured-faster one, DESIGN §4.10): the impulses and "
+                         "tones are generated and scored by the HIP kernels, only their records reach "
+                         "the host; host: NumPy generators and scores (vectors uploaded, round trips "
+                         "downloaded)")
     ap.add_argument("--stub", action="store_true",
                     help="test hook: score nothing on a device; each rank emits one synthetic "
                          "record per vector of its round-robin share (exercises the sharding "
@@ -80,7 +85,7 @@ def main():
         recs = stub_sweep(verify, args.npoints, rank, world, args.max_vectors)
     else:
         recs = verify.purity_sweep(device=local, npoints=args.npoints, batch=args.batch, rank=rank,
-                                   world=world, max_vectors=args.max_vectors)
+                                   world=world, max_vectors=args.max_vectors, scoring=args.scoring)
     if world == 1:
         for r in recs:
             print(json.dumps(r), flush=True)

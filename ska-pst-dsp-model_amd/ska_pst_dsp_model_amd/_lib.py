@@ -50,6 +50,8 @@ PFB_DADA_OUTPUT_STAGED = 2
 PFB_STRIDED_INPUT_NONE = 0
 PFB_STRIDED_INPUT_IN_PLACE = 1
 PFB_STRIDED_INPUT_STAGED = 2
+PFB_TESTVEC_IMPULSE = 0
+PFB_TESTVEC_SINUSOID = 1
 
 _STATUS_NAMES = {value: name for name, value in list(globals().items())
                  if name == "PFB_OK" or name.startswith("PFB_ERR_")}
@@ -182,6 +184,12 @@ SYMBOLS = [
                                   c_void_p, c_int64, c_int64, c_void_p]),
     ("pfb_quantize", c_int32, [c_void_p, c_int64, c_int64, c_int32, c_double, c_void_p, c_int64,
                                POINTER(c_double), c_void_p]),
+    ("pfb_testvec_generate", c_int32, [POINTER(c_int32), POINTER(c_double), c_int32, c_int64, c_void_p,
+                                       c_int64, c_void_p]),
+    ("pfb_purity_score_spurious", c_int32, [c_void_p, c_int32, c_int64, c_int64, c_int32, c_double,
+                                            c_int32, POINTER(c_int64), POINTER(c_double), c_void_p]),
+    ("pfb_purity_score_difference", c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32,
+                                              POINTER(c_double), c_void_p]),
     ("pfb_calc_output_nbins", c_double, [c_int64, c_int32, c_int32, c_int32, c_int64, c_int32,
                                          c_int32]),
     ("pfb_last_error", c_char_p, []),

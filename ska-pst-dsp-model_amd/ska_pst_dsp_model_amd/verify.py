@@ -3,6 +3,9 @@
 ``hip`` backend can be scored exactly as the reference scores its backends.
 
 Host-side NumPy on the (small) metric arrays; the data they score comes off the device.
+``device_vectors`` and ``score_vectors_device`` are the same generators and scores as HIP
+kernels (``csrc/pfb_verify.hip``): the sweep's vectors are made, round-tripped and scored on
+the device, and only the records' doubles reach the host.
 """
 from __future__ import annotations
 
@@ -17,7 +20,8 @@ __all__ = ["spurious", "total_spurious", "mean_spurious", "max_spurious", "dB",
            "max_spurious_power", "total_spurious_power", "mean_spurious_power",
            "temporal_difference", "temporal_performance", "spectral_performance", "chop",
            "performance_alignment", "complex_sinusoid", "time_domain_impulse", "sweep_vectors",
-           "shard", "score_vector", "square_wave_contrast"]
+           "shard", "score_vector", "square_wave_contrast", "device_vectors",
+           "score_vectors_device"]
 
 
 def spurious(a):
@@ -310,6 +314,145 @@ def score_vector(domain: str, param: int, xin, y, al: dict) -> dict:
     return rec
 
 
+# ------------------------------------------------------------------ the same on the device
+def _runs(kinds):
+    """Consecutive runs of equal entries -> [(value, first, end)]."""
+    out = []
+    for i, k in enumerate(kinds):
+        if out and out[-1][0] == k:
+            out[-1][2] = i + 1
+        else:
+            out.append([k, i, i + 1])
+    return [tuple(r) for r in out]
+
+
+def device_vectors(items, n: int, device=0, out=None):
+    """The sweep's impulses and tones generated on the device (pfb_testvec_generate):
+    ``items`` are ("time", p) / ("freq", f) as sweep_vectors returns them -> a
+    (len(items), n) complex64 device tensor whose rows equal time_domain_impulse(n, p) bit for
+    bit and complex_sinusoid(n, f) (phase pi/4) to a float32 rounding.  ``out``: rows of an
+    existing batch tensor to fill instead (row stride >= n, samples contiguous)."""
+    import torch
+    from ctypes import POINTER, c_double, c_int32, c_void_p
+    from . import _lib
+    items = list(items)
+    kind = np.zeros(len(items), np.int32)
+    param = np.zeros((len(items), 4), np.float64)
+    for i, (domain, p) in enumerate(items):
+        if domain == "time":
+            kind[i], param[i, :2] = _lib.PFB_TESTVEC_IMPULSE, (p, 1)
+        elif domain == "freq":
+            kind[i], param[i, :3] = _lib.PFB_TESTVEC_SINUSOID, (p, np.pi / 4, 0.0)
+        else:
+            raise ValueError(f"no device generator for a {domain!r} vector")
+    if out is None:
+        out = torch.empty((len(items), int(n)), dtype=torch.complex64, device=torch.device("cuda", int(device)))
+    if (out.dtype != torch.complex64 or not out.is_cuda or tuple(out.shape) != (len(items), int(n))
+            or (n > 1 and out.stride(1) != 1)):
+        raise ValueError("out must be a (len(items), n) complex64 device tensor with contiguous rows")
+    if not items:
+        return out
+    with torch.cuda.device(out.device):
+        stream = c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
+        _lib.check(_lib.load().pfb_testvec_generate(
+            kind.ctypes.data_as(POINTER(c_int32)), param.ctypes.data_as(POINTER(c_double)), len(items),
+            int(n), c_void_p(out.data_ptr()), int(out.stride(0)) if len(items) > 1 else int(n), stream))
+    return out
+
+
+def _score_spurious(a, n: int, scale: float, domain: int, expected=None):
+    """pfb_purity_score_spurious on the first ``n`` samples of the rows of the 2-D device
+    tensor ``a`` (complex64 or complex128) -> (rows, 6) float64."""
+    import torch
+    from ctypes import POINTER, c_double, c_int64, c_void_p
+    from . import _lib
+    rows = a.shape[0]
+    res = np.zeros((rows, 6), np.float64)
+    exp = None if expected is None else np.ascontiguousarray(expected, dtype=np.int64)
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.load().pfb_purity_score_spurious(
+            c_void_p(a.data_ptr()), 1 if a.dtype == torch.complex128 else 0,
+            int(a.stride(0)) if rows > 1 else max(int(a.stride(0)), int(n)), int(n), rows, float(scale),
+            int(domain), None if exp is None else exp.ctypes.data_as(POINTER(c_int64)),
+            res.ctypes.data_as(POINTER(c_double)), c_void_p(torch.cuda.current_stream(a.device).cuda_stream)))
+    return res
+
+
+def _score_difference(a, b, n: int):
+    """pfb_purity_score_difference on the first ``n`` samples of the rows of the complex64
+    device tensors ``a`` and ``b`` -> (rows, 2) float64: max, sum of |a - b|^2."""
+    import torch
+    from ctypes import POINTER, c_double, c_void_p
+    from . import _lib
+    rows = a.shape[0]
+    res = np.zeros((rows, 2), np.float64)
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.load().pfb_purity_score_difference(
+            c_void_p(a.data_ptr()), int(a.stride(0)) if rows > 1 else max(int(a.stride(0)), int(n)),
+            c_void_p(b.data_ptr()), int(b.stride(0)) if rows > 1 else max(int(b.stride(0)), int(n)),
+            int(n), rows, res.ctypes.data_as(POINTER(c_double)),
+            c_void_p(torch.cuda.current_stream(a.device).cuda_stream)))
+    return res
+
+
+def score_vectors_device(items, x, y, al: dict):
+    """score_vector for a batch on the device: ``x`` (B, n) the generated vectors and ``y``
+    (B, n_out) their round trips, complex64 device tensors with contiguous rows -> one record
+    per item with score_vector's keys and meanings.  chop.m is two offsets and a common
+    length (no copy); the impulses go through pfb_purity_score_spurious (domain 30, with the
+    aligned index as ``expected``), the tones through pfb_purity_score_difference and, for the
+    spectrum, torch.fft.fft of the complex128 series on the device reduced by
+    pfb_purity_score_spurious (scale 1 / fft_length^2, domain 0); the dB fields are formed
+    here from the returned doubles."""
+    import torch
+    items = list(items)
+    if x.dim() != 2 or y.dim() != 2 or x.shape[0] != len(items) or y.shape[0] != len(items):
+        raise ValueError("x and y must be (len(items), n) and (len(items), n_out)")
+    for t in (x, y):
+        if t.dtype != torch.complex64 or not t.is_cuda or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError("x and y must be complex64 device tensors with contiguous rows")
+    to_chomp = int(al["additional_offset"]) - int(al["fir_offset"])
+    if to_chomp < 0:
+        raise ValueError("chop offset below zero (fir_offset beyond additional_offset)")
+    n = min(x.shape[1] - to_chomp, y.shape[1])
+    if n <= 0:
+        raise ValueError("nothing left of the series after chop")
+    fft_length = int(al["fft_length"])
+    recs = [None] * len(items)
+    for domain, i0, i1 in _runs([d for d, _ in items]):
+        params = [int(p) for _, p in items[i0:i1]]
+        inv = y[i0:i1]
+        if domain == "time":
+            exp = [p - 1 - to_chomp for p in params]
+            for i, p, e, r in zip(range(i0, i1), params, exp, _score_spurious(inv, n, 1.0, 30, exp)):
+                rec = {"domain": domain, "param": p, "n_chopped": int(n),
+                       "max_spurious_power": float(r[2]), "total_spurious_power": float(r[3]),
+                       "max_spurious_dB": float(dB(r[2])), "total_spurious_dB": float(dB(r[3]))}
+                if 0 <= e < n:
+                    amp = float(np.sqrt(r[4]))
+                    rec["expected_index"] = e
+                    rec["peak_index"] = int(r[0])
+                    rec["peak_amplitude"] = amp
+                    rec["max_outside_pm1_dB"] = float(20 * np.log10(np.sqrt(r[5]) / max(amp, 1e-30) + 1e-30))
+                recs[i] = rec
+        elif domain == "freq":
+            d = _score_difference(x[i0:i1, to_chomp:], inv, n)
+            # Matlab's fft(a, n) truncates or zero-pads: only the first min(n, fft_length) count
+            spec = torch.fft.fft(inv[:, :min(n, fft_length)].to(torch.complex128), n=fft_length, dim=1)
+            sp = _score_spurious(spec, fft_length, 1.0 / (float(fft_length) * float(fft_length)), 0)
+            del spec
+            for i, p, dd, r in zip(range(i0, i1), params, d, sp):
+                recs[i] = {"domain": domain, "param": p, "n_chopped": int(n),
+                           "max_diff_power": float(dd[0]), "total_diff_power": float(dd[1]),
+                           "mean_diff_power": float(dd[1] / n),
+                           "max_spurious_power": float(r[2]), "total_spurious_power": float(r[3]),
+                           "max_spurious_dB": float(dB(r[2])), "total_spurious_dB": float(dB(r[3])),
+                           "max_diff_dB": float(dB(dd[0]))}
+        else:
+            raise ValueError(f"no device score for a {domain!r} vector")
+    return recs
+
+
 def square_wave_contrast(y, period: int, duty_cycle: float, shift: int, guard: int) -> dict:
     """Not a reference test (sgcht.m:380: 'Testing not implemented for square_wave'):
     mean output power in the on and off phases of the aligned square wave, ``guard``
@@ -358,7 +501,7 @@ def purity_sweep(device=0, npoints: int = 300, batch: int = 16, channels: int = 
                  taps=None, blocks: int = 3, analysis="polyphase_analysis_padded",
                  fir_offset_direction: int = 0, kludge_offset: int = 0, rank: int = 0,
                  world: int = 1, domains=("time", "freq"), extras: bool = True,
-                 max_vectors: int = 0):
+                 max_vectors: int = 0, scoring: str = "host"):
     """BASELINE configs[4]: the test_purity sweep of current_performance.m (sub-config
     'mid': padded bank, 4096 ch, 8/7, 100 353 two-stage taps, Nf 512, Ov 128, tukey,
     deripple, 3 blocks = 5 505 024 samples per vector, fir_offset_direction 0,
@@ -367,7 +510,15 @@ def purity_sweep(device=0, npoints: int = 300, batch: int = 16, channels: int = 
     32-tone frequency comb with TestFrequencyComb.m, the square wave).  Vectors are
     dealt round-robin over ``world`` GPUs (this call runs rank ``rank``'s share) and
     batched ``batch`` at a time as the polarisations of ONE round-trip plan.  Returns
-    one record per vector."""
+    one record per vector.
+
+    ``scoring``: "host" builds every vector with NumPy, uploads it, downloads the round trip
+    and scores it with NumPy; "device" generates the impulses and tones into the batch tensor
+    (device_vectors) and scores them there (score_vectors_device), so only their records reach
+    the host.  The comb and the square wave (2 of 615 vectors; a 32-term double sum and a host
+    RNG) keep the host path in both.  Records, their order and the sharding are the same."""
+    if scoring not in ("host", "device"):
+        raise ValueError(f"scoring must be 'host' or 'device', not {scoring!r}")
     import torch
     from .core import AnalysisPlan, SynthesisPlan, roundtrip
     from .firio import design_PFB_FIR_filter_two_stage
@@ -401,8 +552,17 @@ def purity_sweep(device=0, npoints: int = 300, batch: int = 16, channels: int = 
     out = []
     for i0 in range(0, len(items), batch):
         part = items[i0:i0 + batch]
-        xs = [make(k, p) for k, p in part]
-        x = torch.from_numpy(np.stack(xs)).to(dev)
+        on_dev = [scoring == "device" and k in ("time", "freq") for k, _ in part]
+        xs = [None if d else make(k, p) for (k, p), d in zip(part, on_dev)]
+        if not any(on_dev):
+            x = torch.from_numpy(np.stack(xs)).to(dev)
+        else:
+            x = torch.empty((len(part), n), dtype=torch.complex64, device=dev)
+            for d, j0, j1 in _runs(on_dev):
+                if d:
+                    device_vectors(part[j0:j1], n, out=x[j0:j1])
+                else:
+                    x[j0:j1] = torch.from_numpy(np.stack(xs[j0:j1])).to(dev)
         if len(part) not in plans:
             plans[len(part)] = (
                 AnalysisPlan(taps, channels, o, analysis, len(part), int(device)),
@@ -410,20 +570,27 @@ def purity_sweep(device=0, npoints: int = 300, batch: int = 16, channels: int = 
                               win, None, len(part), int(device)))
         ana, syn = plans[len(part)]
         _, y = roundtrip(ana, syn, x)
-        y = y.cpu().numpy()
-        for (kind, param), xin, yy in zip(part, xs, y):
-            if kind in ("time", "freq"):
-                rec = score_vector(kind, param, xin, yy, al)
-            else:
-                inp, inv = chop(xin, yy, al["fir_offset"], al["additional_offset"])
-                rec = {"domain": kind, "param": int(param), "n_chopped": int(len(inv)),
-                       "power_ratio": float(np.mean(np.abs(inv) ** 2) /
-                                            max(np.mean(np.abs(inp) ** 2), 1e-30))}
-                if kind == "comb":
-                    rec["comb_test"] = frequency_comb_test(inv[None, None, :], f_comb, o, invert=True)
+        recs = [None] * len(part)
+        for d, j0, j1 in _runs(on_dev):
+            if d:
+                recs[j0:j1] = score_vectors_device(part[j0:j1], x[j0:j1], y[j0:j1], al)
+                continue
+            yh = y[j0:j1].cpu().numpy()
+            for j, ((kind, param), xin, yy) in enumerate(zip(part[j0:j1], xs[j0:j1], yh), j0):
+                if kind in ("time", "freq"):
+                    rec = score_vector(kind, param, xin, yy, al)
                 else:
-                    shift = al["additional_offset"] - al["fir_offset"]
-                    rec.update(square_wave_contrast(inv, int(param), 0.5, shift, 64))
+                    inp, inv = chop(xin, yy, al["fir_offset"], al["additional_offset"])
+                    rec = {"domain": kind, "param": int(param), "n_chopped": int(len(inv)),
+                           "power_ratio": float(np.mean(np.abs(inv) ** 2) /
+                                                max(np.mean(np.abs(inp) ** 2), 1e-30))}
+                    if kind == "comb":
+                        rec["comb_test"] = frequency_comb_test(inv[None, None, :], f_comb, o, invert=True)
+                    else:
+                        shift = al["additional_offset"] - al["fir_offset"]
+                        rec.update(square_wave_contrast(inv, int(param), 0.5, shift, 64))
+                recs[j] = rec
+        for rec in recs:
             rec["rank"] = rank
             out.append(rec)
     return out
