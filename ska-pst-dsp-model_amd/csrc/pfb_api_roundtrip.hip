@@ -20,35 +20,56 @@ extern "C" {
 // the same inputs as pfb_analysis_execute + pfb_synthesis_execute, so both results are
 // bit-identical to the separate calls (the fused path below: see its comment).
 
+// One round-trip call.  phase 0: the whole round trip; 1 / 2: only the analysis / only the
+// synthesis half of the fused path (pfb_roundtrip_analysis_execute /
+// pfb_roundtrip_synthesis_execute), which hand the stage-1 rows over in the synthesis plan's
+// scratch.  A half sets the members of its side only.
+struct RtBuf {
+  void* p = nullptr;
+  int64_t ps = 0, cap = 0;  // pol stride; capacity per polarisation
+};
+struct RtCall {
+  int phase = 0;
+  int64_t n_dat = 0, sample_offset = 1;
+  // input and channelised product (phase != 2): cf32 [pol][t] and [pol][row][chan], capacity in
+  // rows — or, with RtOpt::dd / od, the sections themselves
+  const void* in = nullptr;
+  int64_t in_ps = 0;
+  RtBuf chan;
+  // output (phase != 1): cf32 [pol][t], capacity in samples — or, with RtOpt::sd, the section
+  RtBuf out;
+  int64_t* n_chan_rows = nullptr;
+  int64_t* n_out = nullptr;
+  void* stream = nullptr;
+};
+
 // What the file-to-file calls (roundtrip_dada, below) ask of roundtrip_run; the cf32 calls pass
 // none of it.
 struct RtOpt {
   // FUSED: the analysis launch reads the section dd in place and stores the product as the
-  // float section od (`in` and `chan` then only have to pass the checks); the synthesis stores
-  // through the plan's dout, which the caller sets.  Only for a call that `wave2` named.
+  // float section od, and the block launch stores the section sd.  Only for a call that
+  // `wave2` named.
   const AnaDada* dd = nullptr;
   const AnaOut* od = nullptr;
+  SynthDada sd;
   // the stage-1 rows are stored whatever pfb_synthesis_set_stage1_rows says (no recomputing
   // kernel reads a section, and a plan-owned staging buffer is no input to come back to)
   bool stored = false;
-  // every check of the call and the allocation of the rows, then return: no launch, no change
-  // of the split round trip's key
+  // every check of the call but those of the pol strides (sections have none), and the
+  // allocation of the rows, then return: no launch, no change of the split round trip's key
   bool dry = false;
   // (dry) set when the call takes the fused path through the streaming analysis and the
   // Nf = 256 wave kernel on stored 2-row runs
   bool* wave2 = nullptr;
 };
 
-// phase 0: the whole round trip; 1 / 2: only the analysis / only the synthesis half of the
-// fused path (pfb_roundtrip_analysis_execute / pfb_roundtrip_synthesis_execute), which hand
-// the stage-1 rows over in the synthesis plan's scratch
-static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, const pfb_cf32* in,
-                                int64_t in_ps, int64_t n_dat, pfb_cf32* chan, int64_t chan_ps,
-                                int64_t chan_cap, int64_t* n_chan_rows, int64_t sample_offset,
-                                pfb_cf32* out, int64_t out_ps, int64_t out_cap, int64_t* n_out,
-                                void* stream, int phase, const RtOpt& opt = RtOpt{}) {
+static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, const RtCall& c, const RtOpt& opt) {
+  const int phase = c.phase;
+  const int64_t n_dat = c.n_dat, sample_offset = c.sample_offset, in_ps = c.in_ps, chan_ps = c.chan.ps;
+  const float2* x = static_cast<const float2*>(c.in);
+  float2* y = static_cast<float2*>(c.chan.p);
   if (opt.wave2) *opt.wave2 = false;
-  if (!pa || !ps || (!in && n_dat > 0 && phase != 2)) return fail(PFB_ERR_INVALID_ARG, "null argument");
+  if (!pa || !ps || (!x && n_dat > 0 && phase != 2)) return fail(PFB_ERR_INVALID_ARG, "null argument");
   if (pa->device != ps->device) return fail(PFB_ERR_INVALID_ARG, "plans on different devices");
   if (pa->variant == pfb::kLowCbf)
     return fail(PFB_ERR_UNSUPPORTED, "round trip of the LowCBF filterbank: use the separate calls");
@@ -58,29 +79,28 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
   if (sample_offset < 1) return fail(PFB_ERR_INVALID_ARG, "sample_offset is 1-based (>= 1)");
   if (n_dat < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_dat");
   HIPCHK(hipSetDevice(pa->device));
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = (hipStream_t)c.stream;
   const int64_t K = analysis_K(pa, n_dat);
   const int64_t off = std::min<int64_t>(sample_offset - 1, K);
   const int64_t B = synth_blocks(ps, K - off);
   const int64_t olen = B * ps->Lkeep;
-  if (n_chan_rows) *n_chan_rows = K;
-  if (n_out) *n_out = olen;
+  if (c.n_chan_rows) *c.n_chan_rows = K;
+  if (c.n_out) *c.n_out = olen;
   if (K == 0) return PFB_OK;
   if (phase != 2) {
-    if (!chan) return fail(PFB_ERR_INVALID_ARG, "null output");
-    if (chan_cap < K) return fail(PFB_ERR_BUFFER_TOO_SMALL, "channelised capacity %lld < %lld rows",
-                                  (long long)chan_cap, (long long)K);
-    if (in_ps < n_dat || chan_ps < K * pa->N)
+    if (!y) return fail(PFB_ERR_INVALID_ARG, "null output");
+    if (c.chan.cap < K) return fail(PFB_ERR_BUFFER_TOO_SMALL, "channelised capacity %lld < %lld rows",
+                                    (long long)c.chan.cap, (long long)K);
+    if (!opt.dry && (in_ps < n_dat || chan_ps < K * pa->N))
       return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
   }
   if (phase != 1) {
-    if (olen > 0 && !out) return fail(PFB_ERR_INVALID_ARG, "null output");
-    if (out_cap < olen) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld",
-                                    (long long)out_cap, (long long)olen);
-    if (olen > 0 && out_ps < olen) return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
+    if (olen > 0 && !c.out.p) return fail(PFB_ERR_INVALID_ARG, "null output");
+    if (c.out.cap < olen) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld",
+                                      (long long)c.out.cap, (long long)olen);
+    if (!opt.dry && olen > 0 && c.out.ps < olen)
+      return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
   }
-  const float2* x = (const float2*)in;
-  float2* y = (float2*)chan;
   // the analysis of the whole call: all K rows into `chan` (the launches below add to it)
   AnaLaunch whole;
   whole.in = x;
@@ -91,7 +111,7 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
   whole.K_end = whole.K_total = K;
   if (B == 0) return (phase == 2 || opt.dry) ? PFB_OK : analysis_run(pa, whole, s);
   // the block-kernel arguments of all B blocks, no buffers set: what the shape predicates read
-  auto blocks_probe = [&](int zb, const FirSrc* f = nullptr) {
+  auto blocks_probe = [&](int zb, const FirSrc* f) {
     SynthLaunch l;
     l.nb = B;
     l.zblk = zb;
@@ -119,7 +139,7 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
   static const bool no_wave = pfb::knob("PFB_SYNTH_WAVE") && std::atoi(pfb::knob("PFB_SYNTH_WAVE")) == 0;
   static const int zb_knob = pfb::knob("PFB_ZBLK") ? std::atoi(pfb::knob("PFB_ZBLK")) : 2;
   int zblk = (!no_wave && analysis_emits_zblk(pa) && z0 == off && off % 16 == 0) ? zb_knob : 0;
-  if (zblk && !pfb::synth_wave_supported(blocks_probe(zblk))) zblk = 0;
+  if (zblk && !pfb::synth_wave_supported(blocks_probe(zblk, nullptr))) zblk = 0;
   // generic path (N > 256, the SKA-Mid round trip): the FIR writes the rows in 2-row runs
   // per column, so the Nf = 512 wave synthesis loads whole 128-B lines (2 rows x 8 phases)
   // — bit-identical; measured (profiles/r05_v17_c3_zrun_kernel_ab/) synthesis -17 us, FIR
@@ -127,7 +147,7 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
   // earlier): net -5 us per unit (PFB_C3_ZRUN=0: rows, experiments build)
   static const bool zrun_on = !(pfb::knob("PFB_C3_ZRUN") && std::atoi(pfb::knob("PFB_C3_ZRUN")) == 0);
   const bool zrun = zrun_on && !zblk && !pa->fused && analysis_emits_z(pa) && off % 2 == 0 &&
-                    pfb::synth_wave512_supported(blocks_probe(2));
+                    pfb::synth_wave512_supported(blocks_probe(2, nullptr));
   if (zrun) zblk = 2;
   const int64_t zrows = zrun ? (zr + 1) / 2 * 2 : zblk ? (zr + 15) / 16 * 16 : zr;
   const size_t zbytes = (size_t)pa->n_pol * zrows * pa->N * sizeof(float2);
@@ -140,7 +160,7 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
   // (pfb_synthesis_set_stage1_rows).
   const bool synth_fir_on =
       !opt.stored && (ps->stage1 == PFB_STAGE1_RECOMPUTED || (ps->stage1 == PFB_STAGE1_AUTO && kSynthFirDefault));
-  FirSrc fsrc{(const float2*)in, in_ps, n_dat, off / std::max(pa->nu, 1), pa->gtab.as<float>(), pa->nu, pa->de,
+  FirSrc fsrc{x, in_ps, n_dat, off / std::max(pa->nu, 1), pa->gtab.as<float>(), pa->nu, pa->de,
               pa->P + 1};
   bool fir = false;
   if (synth_fir_on && zblk && pa->gtab.p && off % pa->nu == 0 && phase != 2) {
@@ -157,9 +177,8 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
   // from the rows in Z (set below, with the analysis launch that writes them)
   SynthLaunch blocks;
   blocks.nb = B;
-  blocks.out = (float2*)out;
-  blocks.out_ps = out_ps;
-  blocks.out_limit = olen;
+  blocks.o = opt.sd.base ? SynthOut{nullptr, c.out.ps, olen, opt.sd}
+                         : SynthOut{static_cast<float2*>(c.out.p), c.out.ps, olen, {}};
   if (fir && fuse) {
     blocks.fir = &fsrc;
     if (phase == 2) {
@@ -180,7 +199,7 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
       // the synthesis half re-reads this input: the caller keeps it unchanged until then
       ps->zkey_plan = pa->serial;
       std::copy(zkey, zkey + 5, ps->zkey);
-      ps->zkey_x = in;
+      ps->zkey_x = x;
       ps->zkey_xps = in_ps;
       return PFB_OK;
     }
@@ -299,7 +318,7 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
     ra = rb;
     HIPCHK(hipEventRecord(pa->events[1 + c], pa->aux));
     HIPCHK(hipStreamWaitEvent(s, pa->events[1 + c], 0));
-    st = synthesis_chunk(ps, sin_, chan_ps, b0, nb, (float2*)out, out_ps, olen, s);
+    st = synthesis_chunk(SynthRows::packed(ps, sin_, chan_ps, K - off), Blocks{b0, b0 + nb}, blocks.o, s);
     if (st != PFB_OK) return st;
   }
   // join (the last chunk already ran the analysis to K)
@@ -308,28 +327,50 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
   return PFB_OK;
 }
 
+// the request of an entry point, without its buffers
+static RtCall rt_call(int phase, int64_t n_dat, int64_t sample_offset, void* stream) {
+  RtCall c;
+  c.phase = phase;
+  c.n_dat = n_dat;
+  c.sample_offset = sample_offset;
+  c.stream = stream;
+  return c;
+}
+
 pfb_status pfb_roundtrip_execute(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, const pfb_cf32* in,
                                  int64_t in_ps, int64_t n_dat, pfb_cf32* chan, int64_t chan_ps,
                                  int64_t chan_cap, int64_t* n_chan_rows, int64_t sample_offset,
                                  pfb_cf32* out, int64_t out_ps, int64_t out_cap, int64_t* n_out,
                                  void* stream) {
-  return roundtrip_run(pa, ps, in, in_ps, n_dat, chan, chan_ps, chan_cap, n_chan_rows, sample_offset,
-                       out, out_ps, out_cap, n_out, stream, 0);
+  RtCall c = rt_call(0, n_dat, sample_offset, stream);
+  c.in = in;
+  c.in_ps = in_ps;
+  c.chan = RtBuf{chan, chan_ps, chan_cap};
+  c.n_chan_rows = n_chan_rows;
+  c.out = RtBuf{out, out_ps, out_cap};
+  c.n_out = n_out;
+  return roundtrip_run(pa, ps, c, RtOpt{});
 }
 
 pfb_status pfb_roundtrip_analysis_execute(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, const pfb_cf32* in,
                                           int64_t in_ps, int64_t n_dat, pfb_cf32* chan, int64_t chan_ps,
                                           int64_t chan_cap, int64_t* n_chan_rows, int64_t sample_offset,
                                           void* stream) {
-  return roundtrip_run(pa, ps, in, in_ps, n_dat, chan, chan_ps, chan_cap, n_chan_rows, sample_offset,
-                       nullptr, 0, 0, nullptr, stream, 1);
+  RtCall c = rt_call(1, n_dat, sample_offset, stream);
+  c.in = in;
+  c.in_ps = in_ps;
+  c.chan = RtBuf{chan, chan_ps, chan_cap};
+  c.n_chan_rows = n_chan_rows;
+  return roundtrip_run(pa, ps, c, RtOpt{});
 }
 
 pfb_status pfb_roundtrip_synthesis_execute(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, int64_t n_dat,
                                            int64_t sample_offset, pfb_cf32* out, int64_t out_ps,
                                            int64_t out_cap, int64_t* n_out, void* stream) {
-  return roundtrip_run(pa, ps, nullptr, n_dat, n_dat, nullptr, 0, 0, nullptr, sample_offset, out, out_ps,
-                       out_cap, n_out, stream, 2);
+  RtCall c = rt_call(2, n_dat, sample_offset, stream);
+  c.out = RtBuf{out, out_ps, out_cap};
+  c.n_out = n_out;
+  return roundtrip_run(pa, ps, c, RtOpt{});
 }
 
 // ---- the round trip from a DADA section into DADA sections (pfb_api.h)
@@ -357,13 +398,15 @@ static bool roundtrip_dada_in_fusable(const pfb_analysis_plan* p, const DadaSect
   return pfb::stream_rt_dada_supported(analysis_shape(p), sec.nbit);
 }
 
-// phase: roundtrip_run's.  Every check — roundtrip_run's own among them, through its dry run —
-// comes before the first launch and before the split round trip's key changes; then FUSED (the
+// `call`: the request without its buffers (phase, n_dat, sample_offset, the two out-lengths,
+// the stream).  Every check — roundtrip_run's own among them, through its dry run — comes
+// before the first launch and before the split round trip's key changes; then FUSED (the
 // analysis launch reads and stores the sections, the wave synthesis stores the output section)
 // or STAGED (unpack, the cf32 round trip on plan-owned buffers, the packs).
-static pfb_status roundtrip_dada(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, const RtSections& sec, int64_t n_dat,
-                                 int64_t* n_chan_rows, int64_t sample_offset, int64_t* n_out, void* stream,
-                                 int phase) {
+static pfb_status roundtrip_dada(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, const RtSections& sec,
+                                 const RtCall& call) {
+  const int phase = call.phase;
+  const int64_t n_dat = call.n_dat;
   if (!pa || !ps) return fail(PFB_ERR_INVALID_ARG, "null plan");
   if (phase != 2) {
     const pfb_status st = section_check(pa, sec.in, n_dat);
@@ -380,57 +423,52 @@ static pfb_status roundtrip_dada(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, 
     if (reinterpret_cast<uintptr_t>(sec.out) % (size_t)(sec.out_nbit / 8) != 0)
       return fail(PFB_ERR_INVALID_ARG, "output section not aligned to its NBIT");
   }
-  // the cf32 call's checks, in its order, with the capacities in its units: whole rows of the
-  // product section, whole samples (all polarisations) of the output section
-  const int64_t big = INT64_MAX / 4;  // (a stride that passes: nothing is launched)
-  const int64_t chan_cap = phase != 2 ? std::max<int64_t>(sec.chan_cap_bytes, 0) / ((int64_t)pa->N * pa->n_pol * 8) : 0;
-  const int64_t out_cap =
-      phase != 1 ? std::max<int64_t>(sec.out_cap_bytes, 0) / ((int64_t)ps->n_pol * 2 * (sec.out_nbit / 8)) : 0;
-  const pfb_cf32* in_c = static_cast<const pfb_cf32*>(sec.in.base);
-  pfb_cf32* chan_c = static_cast<pfb_cf32*>(sec.chan);
-  pfb_cf32* out_c = static_cast<pfb_cf32*>(sec.out);
+  // the cf32 call's checks, in its order, on the sections themselves, with the capacities in
+  // its units: whole rows of the product section, whole samples (all polarisations) of the
+  // output section
   int64_t K = 0, olen = 0;
   bool wave2 = false;
-  RtOpt dry;
-  dry.stored = true;
-  dry.dry = true;
-  dry.wave2 = &wave2;
-  pfb_status st = phase == 2 ? roundtrip_run(pa, ps, nullptr, n_dat, n_dat, nullptr, 0, 0, &K, sample_offset, out_c,
-                                             big, out_cap, &olen, stream, 2, dry)
-                             : roundtrip_run(pa, ps, in_c, big, n_dat, chan_c, big, chan_cap, &K, sample_offset,
-                                             out_c, big, phase == 1 ? 0 : out_cap, &olen, stream, phase, dry);
-  if (n_chan_rows && phase != 2) *n_chan_rows = K;
-  if (n_out && phase != 1) *n_out = olen;
+  RtCall c = call;
+  c.n_chan_rows = &K;
+  c.n_out = &olen;
+  if (phase != 2) {
+    c.in = sec.in.base;
+    c.chan = RtBuf{sec.chan, 0, std::max<int64_t>(sec.chan_cap_bytes, 0) / ((int64_t)pa->N * pa->n_pol * 8)};
+  }
+  if (phase != 1)
+    c.out = RtBuf{sec.out, 0, std::max<int64_t>(sec.out_cap_bytes, 0) / ((int64_t)ps->n_pol * 2 * (sec.out_nbit / 8))};
+  RtOpt opt;
+  opt.stored = true;
+  opt.dry = true;
+  opt.wave2 = &wave2;
+  pfb_status st = roundtrip_run(pa, ps, c, opt);
+  if (call.n_chan_rows && phase != 2) *call.n_chan_rows = K;
+  if (call.n_out && phase != 1) *call.n_out = olen;
   if (st != PFB_OK || K == 0) return st;
   if (phase == 2 && olen == 0) return PFB_OK;
 
-  hipStream_t s = (hipStream_t)stream;
+  // the call itself: packed strides and exact capacities, nothing left to report
+  hipStream_t s = (hipStream_t)call.stream;
   const int P = pa->n_pol;
+  opt.dry = false;
+  opt.wave2 = nullptr;
+  c.n_chan_rows = c.n_out = nullptr;
+  c.in_ps = n_dat;
+  c.chan = RtBuf{c.chan.p, K * pa->N, K};
+  c.out = RtBuf{c.out.p, olen, olen};
   const bool in_fused = phase != 2 && roundtrip_dada_in_fusable(pa, sec.in, sec.chan);
   const bool out_fused = phase != 1 && synthesis_dada_out_fusable(ps, sec.out, sec.out_nbit);
   const bool cell = phase == 0 && rt_dada_cell_staged(P, sec.in.nbit, sec.out_nbit);
-  const bool fused = wave2 && !cell && (phase == 2 || in_fused) && (phase == 1 || out_fused);
-  RtOpt run;
-  run.stored = true;
-  if (fused) {
-    // (the sections stand in for the cf32 buffers in the callee's checks; the launches go
-    // through dd / od and the synthesis plan's dout only)
+  if (wave2 && !cell && (phase == 2 || in_fused) && (phase == 1 || out_fused)) {
+    // FUSED: the launches go through dd / od / sd (c.in, c.chan.p and c.out.p stay the sections)
     const AnaDada dd{sec.in.base, sec.in.nbit};
     const AnaOut od{sec.chan, 32, 1.0f};
     if (phase != 2) {
-      run.dd = &dd;
-      run.od = &od;
+      opt.dd = &dd;
+      opt.od = &od;
     }
-    if (phase != 1) {
-      ps->dout = sec.out;
-      ps->dout_nbit = sec.out_nbit;
-      ps->dout_scale = sec.out_scale;
-    }
-    st = phase == 2 ? roundtrip_run(pa, ps, nullptr, n_dat, n_dat, nullptr, 0, 0, nullptr, sample_offset, out_c, olen,
-                                    olen, nullptr, stream, 2, run)
-                    : roundtrip_run(pa, ps, in_c, n_dat, n_dat, chan_c, K * pa->N, K, nullptr, sample_offset, out_c,
-                                    olen, olen, nullptr, stream, phase, run);
-    ps->dout = nullptr;
+    if (phase != 1) opt.sd = SynthDada{sec.out, sec.out_nbit, sec.out_scale};
+    st = roundtrip_run(pa, ps, c, opt);
     if (st != PFB_OK) return st;
     if (phase != 2) pa->last_dada_out = PFB_DADA_OUTPUT_FUSED;  // (last_dada: analysis_run, FUSED)
     if (phase != 1) ps->last_dada_out = PFB_DADA_OUTPUT_FUSED;
@@ -462,15 +500,14 @@ static pfb_status roundtrip_dada(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, 
     st = section_unpack(pa, sec.in, 0, n_dat, x, n_dat, s);
     if (st != PFB_OK) return st;
   }
-  st = phase == 2 ? roundtrip_run(pa, ps, nullptr, n_dat, n_dat, nullptr, 0, 0, nullptr, sample_offset,
-                                  reinterpret_cast<pfb_cf32*>(o), olen, olen, nullptr, stream, 2, run)
-                  : roundtrip_run(pa, ps, reinterpret_cast<const pfb_cf32*>(x), n_dat, n_dat,
-                                  reinterpret_cast<pfb_cf32*>(y), K * pa->N, K, nullptr, sample_offset,
-                                  reinterpret_cast<pfb_cf32*>(o), olen, olen, nullptr, stream, phase, run);
+  c.in = x;
+  c.chan.p = y;
+  c.out.p = o;
+  st = roundtrip_run(pa, ps, c, opt);
   if (st != PFB_OK) return st;
   if (phase != 2) {
     if (!chan_direct) {
-      st = pfb_dada_pack(reinterpret_cast<const pfb_cf32*>(y), K * pa->N, K, pa->N, P, sec.chan, 32, stream);
+      st = pfb_dada_pack(reinterpret_cast<const pfb_cf32*>(y), K * pa->N, K, pa->N, P, sec.chan, 32, call.stream);
       if (st != PFB_OK) return st;
     }
     pa->last_dada = PFB_DADA_INPUT_STAGED;
@@ -489,7 +526,10 @@ pfb_status pfb_roundtrip_execute_dada_to_dada(pfb_analysis_plan* pa, pfb_synthes
                                               void* out, int32_t out_nbit, float out_scale, int64_t out_cap_bytes,
                                               int64_t* n_out, void* stream) {
   const RtSections sec{DadaSection{in, nbit, ndim, order}, chan, chan_cap_bytes, out, out_nbit, out_scale, out_cap_bytes};
-  return roundtrip_dada(pa, ps, sec, n_dat, n_chan_rows, sample_offset, n_out, stream, 0);
+  RtCall c = rt_call(0, n_dat, sample_offset, stream);
+  c.n_chan_rows = n_chan_rows;
+  c.n_out = n_out;
+  return roundtrip_dada(pa, ps, sec, c);
 }
 
 pfb_status pfb_roundtrip_analysis_execute_dada(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, const void* in,
@@ -497,7 +537,9 @@ pfb_status pfb_roundtrip_analysis_execute_dada(pfb_analysis_plan* pa, pfb_synthe
                                                int64_t chan_cap_bytes, int64_t* n_chan_rows, int64_t sample_offset,
                                                void* stream) {
   const RtSections sec{DadaSection{in, nbit, ndim, order}, chan, chan_cap_bytes, nullptr, 0, 1.f, 0};
-  return roundtrip_dada(pa, ps, sec, n_dat, n_chan_rows, sample_offset, nullptr, stream, 1);
+  RtCall c = rt_call(1, n_dat, sample_offset, stream);
+  c.n_chan_rows = n_chan_rows;
+  return roundtrip_dada(pa, ps, sec, c);
 }
 
 pfb_status pfb_roundtrip_synthesis_execute_to_dada(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, int64_t n_dat,
@@ -505,7 +547,9 @@ pfb_status pfb_roundtrip_synthesis_execute_to_dada(pfb_analysis_plan* pa, pfb_sy
                                                    float out_scale, int64_t out_cap_bytes, int64_t* n_out,
                                                    void* stream) {
   const RtSections sec{DadaSection{nullptr, 0, 0, 0}, nullptr, 0, out, out_nbit, out_scale, out_cap_bytes};
-  return roundtrip_dada(pa, ps, sec, n_dat, nullptr, sample_offset, n_out, stream, 2);
+  RtCall c = rt_call(2, n_dat, sample_offset, stream);
+  c.n_out = n_out;
+  return roundtrip_dada(pa, ps, sec, c);
 }
 
 }  // extern "C"

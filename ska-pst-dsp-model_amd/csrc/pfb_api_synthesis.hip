@@ -46,8 +46,8 @@ pfb::SynthBlockArgs pfb::host::synth_args(const pfb_synthesis_plan* p, const Syn
   }
   a.Z = l.Z;
   a.z_pol_stride = l.z_ps;
-  a.out = l.out;
-  a.out_pol_stride = l.out_ps;
+  a.out = l.o.out;
+  a.out_pol_stride = l.o.out_ps;
   a.block0 = l.b0;
   a.n_blocks = (int)l.nb;
   a.n_pol = p->n_pol;
@@ -68,15 +68,15 @@ pfb::SynthBlockArgs pfb::host::synth_args(const pfb_synthesis_plan* p, const Syn
   a.tw4s = p->tw4s.as<float2>();
   a.twNf = p->twNf.as<float2>();
   a.twW = p->twW.as<float2>();
-  a.out_limit = l.out_limit;
+  a.out_limit = l.o.out_limit;
   a.ranges = p->ranges;
   a.no_reuse = p->no_reuse;
   a.xcd = p->xcd;
   a.timing_mask = p->timing_mask;
   a.zblk = l.zblk;
-  a.dout = p->dout;
-  a.dout_nbit = p->dout_nbit;
-  a.dout_scale = p->dout_scale;
+  a.dout = l.o.dada.base;
+  a.dout_nbit = l.o.dada.nbit;
+  a.dout_scale = l.o.dada.scale;
   return a;
 }
 
@@ -90,27 +90,68 @@ pfb_status pfb::host::synthesis_blocks(pfb_synthesis_plan* p, const SynthLaunch&
   return PFB_OK;
 }
 
-// Blocks [b0, b0 + nb) with a spectral taper (pfb_spectral.hip): Matlab's order — per
-// channel FFT, stitch x taper, then the L-point IFFT as row FFTs — in sub-chunks whose
-// scratch stays within 2^26 values per buffer.
-static pfb_status synthesis_spectral(pfb_synthesis_plan* p, const float2* in, int64_t in_ps, int64_t b0,
-                                     int64_t nb, float2* out, int64_t out_ps, int64_t out_limit,
-                                     hipStream_t s) {
+pfb_status SynthRows::chan_in(int64_t r, int64_t n, pfb::ChanIfftArgs& c) {
+  switch (kind) {
+    case DADA:
+      dada.t0 = r;
+      if (r < 0 || r + n > rows) return fail(PFB_ERR_INVALID_ARG, "rows outside the DADA section");
+      c.dada = &dada;
+      plan->last_dada = PFB_DADA_INPUT_FUSED;
+      break;
+    case STRIDED:
+      strided.t0 = r;
+      if (r < 0 || r + n > rows) return fail(PFB_ERR_INVALID_ARG, "rows outside the strided input");
+      c.strided = &strided;
+      plan->last_strided = PFB_STRIDED_INPUT_IN_PLACE;
+      break;
+    case PACKED:
+      c.in = base + r * plan->N;
+      c.in_pol_stride = ps;
+      break;
+  }
+  return PFB_OK;
+}
+
+hipError_t SynthRows::copy_to(int64_t r, int64_t n, float2* dst, int64_t dps, hipStream_t s) const {
+  pfb_synthesis_plan* p = plan;
+  switch (kind) {
+    case DADA: {
+      pfb::DadaIn d = dada;
+      d.t0 = r;
+      if (p->last_dada == PFB_DADA_INPUT_NONE) p->last_dada = PFB_DADA_INPUT_STAGED;
+      return pfb::launch_dada_unpack_rows(d, n, p->N, p->n_pol, dst, dps, s);
+    }
+    case STRIDED: {
+      pfb::StridedIn d = strided;
+      d.t0 = r;
+      if (p->last_strided == PFB_STRIDED_INPUT_NONE) p->last_strided = PFB_STRIDED_INPUT_STAGED;
+      return pfb::launch_strided_rows_copy(d, n, p->N, p->n_pol, dst, dps, s);
+    }
+    case PACKED: break;
+  }
+  return copy_pols(dst, dps, base + r * p->N, ps, n * p->N, p->n_pol, copy, s);
+}
+
+// Blocks b with a spectral taper (pfb_spectral.hip): Matlab's order — per channel FFT, stitch
+// x taper, then the L-point IFFT as row FFTs — in sub-chunks whose scratch stays within 2^26
+// values per buffer.  Packed rows only, none of the call's missing from them.
+static pfb_status synthesis_spectral(const SynthRows& rows, Blocks b, const SynthOut& out, hipStream_t s) {
+  pfb_synthesis_plan* p = rows.plan;
   p->last_stage1 = PFB_STAGE1_STORED;  // (the spectral passes read the channelised rows)
   const int64_t per_block = (int64_t)p->N * std::max(p->Nf, p->W);
   const int64_t sub = std::max<int64_t>(1, std::min<int64_t>(65535, ((int64_t)1 << 26) / per_block));
-  const int64_t nsub = std::min(sub, nb);
+  const int64_t nsub = std::min(sub, b.hi - b.lo);
   HIPCHK(p->sbuf0.ensure((size_t)nsub * per_block * sizeof(float2)));
   HIPCHK(p->sbuf1.ensure((size_t)nsub * per_block * sizeof(float2)));
-  for (int64_t c0 = b0; c0 < b0 + nb; c0 += nsub) {
+  for (int64_t c0 = b.lo; c0 < b.hi; c0 += nsub) {
     pfb::SpectralArgs a{};
-    a.in = in;
-    a.in_pol_stride = in_ps;
-    a.out = out;
-    a.out_pol_stride = out_ps;
-    a.out_limit = out_limit;
+    a.in = rows.base + rows.row0 * p->N;
+    a.in_pol_stride = rows.ps;
+    a.out = out.out;
+    a.out_pol_stride = out.out_ps;
+    a.out_limit = out.out_limit;
     a.b0 = c0;
-    a.nb = std::min(nsub, b0 + nb - c0);
+    a.nb = std::min(nsub, b.hi - c0);
     a.n_pol = p->n_pol;
     a.N = p->N;
     a.Nf = p->Nf;
@@ -139,49 +180,26 @@ static pfb_status synthesis_spectral(pfb_synthesis_plan* p, const float2* in, in
   return PFB_OK;
 }
 
-// Blocks [b0, b0 + nb) of a call: channel IFFT of their rows into Z, then the block
-// kernel.  `in` is the call's first channelised row (sample_offset applied).
-// (row_shift: `in` holds the call's channelised rows from row row_shift on — a streaming
-// call whose carried rows are not in front of it; blocks b0.. must not read before it.  A
-// negative row_shift: block 0 starts -row_shift rows into `in` (InverseFilterBank's
-// sample_offset applied to the concatenated rows))
-// (dada: the call's rows are a DADA section read in place, `in` is unused — the section's
-// row 0 is the call's row row_shift; strided: the same for rows behind a strided layout)
-pfb_status pfb::host::synthesis_chunk(pfb_synthesis_plan* p, const float2* in, int64_t in_ps, int64_t b0, int64_t nb,
-                                      float2* out, int64_t out_ps, int64_t out_limit, hipStream_t s,
-                                      int64_t row_shift, const pfb::DadaIn* dada, const pfb::StridedIn* strided) {
+// Blocks b of a call: channel IFFT of their rows into Z, then the block kernel.
+// (`rows` by value: the channel IFFT's arguments point into it, SynthRows::chan_in)
+pfb_status pfb::host::synthesis_chunk(SynthRows rows, Blocks b, const SynthOut& out, hipStream_t s) {
+  pfb_synthesis_plan* p = rows.plan;
   if (p->has_spectral) {
-    if (dada || strided) return fail(PFB_ERR_UNSUPPORTED, "rows read in place with a spectral taper");
-    // (a negative row shift: the blocks start -row_shift rows into `in` — a sample offset)
-    if (row_shift > 0) return fail(PFB_ERR_UNSUPPORTED, "row shift with a spectral taper");
-    return synthesis_spectral(p, in + (-row_shift) * p->N, in_ps, b0, nb, out, out_ps, out_limit, s);
+    if (rows.kind != SynthRows::PACKED) return fail(PFB_ERR_UNSUPPORTED, "rows read in place with a spectral taper");
+    // (a positive row0: the blocks start that many rows into the rows — a sample offset)
+    if (rows.row0 < 0) return fail(PFB_ERR_UNSUPPORTED, "row shift with a spectral taper");
+    return synthesis_spectral(rows, b, out, s);
   }
-  const int64_t rows = nb * p->keep + 2 * (int64_t)p->Ov;
+  const int64_t n = (b.hi - b.lo) * p->keep + 2 * (int64_t)p->Ov;
   zkey_clear(p);
-  HIPCHK(p->Z.ensure((size_t)p->n_pol * rows * p->N * sizeof(float2)));
+  HIPCHK(p->Z.ensure((size_t)p->n_pol * n * p->N * sizeof(float2)));
   float2* Z = p->Z.as<float2>();
   pfb::ChanIfftArgs c{};
-  pfb::DadaIn dd{};
-  pfb::StridedIn sd{};
-  if (dada) {
-    dd = *dada;
-    dd.t0 = b0 * p->keep - row_shift;
-    if (dd.t0 < 0 || dd.t0 + rows > dd.n_dat) return fail(PFB_ERR_INVALID_ARG, "rows outside the DADA section");
-    c.dada = &dd;
-    p->last_dada = PFB_DADA_INPUT_FUSED;
-  } else if (strided) {
-    sd = *strided;
-    sd.t0 = b0 * p->keep - row_shift;
-    if (sd.t0 < 0 || sd.t0 + rows > sd.n_dat) return fail(PFB_ERR_INVALID_ARG, "rows outside the strided input");
-    c.strided = &sd;
-    p->last_strided = PFB_STRIDED_INPUT_IN_PLACE;
-  } else {
-    c.in = in + (b0 * p->keep - row_shift) * p->N;
-  }
-  c.in_pol_stride = in_ps;
+  const pfb_status st = rows.chan_in(rows.row0 + b.lo * p->keep, n, c);
+  if (st != PFB_OK) return st;
   c.out = Z;
-  c.out_pol_stride = rows * p->N;
-  c.n_rows = rows;
+  c.out_pol_stride = n * p->N;
+  c.n_rows = n;
   c.n_pol = p->n_pol;
   c.N = p->N;
   c.perm = p->identity_perm ? nullptr : p->perm.as<int>();
@@ -192,18 +210,16 @@ pfb_status pfb::host::synthesis_chunk(pfb_synthesis_plan* p, const float2* in, i
   // [row][t0] for the block kernel
   SynthLaunch l;
   l.Z = Z;
-  l.z_ps = rows * p->N;
-  l.b0 = b0;
-  l.nb = nb;
-  l.out = out;
-  l.out_ps = out_ps;
-  l.out_limit = out_limit;
+  l.z_ps = n * p->N;
+  l.b0 = b.lo;
+  l.nb = b.hi - b.lo;
+  l.o = out;
   l.zblk = 2;
   if (!pfb::synth_wave_supported(synth_args(p, l))) l.zblk = 0;
   c.zblk = l.zblk ? l.zblk : 1;
   {
-    const double in_bytes = dada ? 2.0 * (dada->nbit / 8) : 8.0;
-    ProfScope ps(1, (double)p->n_pol * rows * p->N * (in_bytes + 8.0), s);
+    const double in_bytes = rows.kind == SynthRows::DADA ? 2.0 * (rows.dada.nbit / 8) : 8.0;
+    ProfScope ps(1, (double)p->n_pol * n * p->N * (in_bytes + 8.0), s);
     HIPCHK(pfb::launch_chan_ifft(c, s));
   }
   return synthesis_blocks(p, l, s);
@@ -220,24 +236,15 @@ static int64_t synthesis_chunk_blocks(const pfb_synthesis_plan* p, int64_t B) {
   return std::min<int64_t>(CB, B);
 }
 
-// blocks [b_lo, b_hi) in chunks (see synthesis_chunk for row_shift)
-static pfb_status synthesis_range(pfb_synthesis_plan* p, const float2* in, int64_t in_ps, int64_t b_lo,
-                                  int64_t b_hi, float2* out, int64_t out_ps, int64_t out_limit,
-                                  hipStream_t s, int64_t row_shift = 0, const pfb::DadaIn* dada = nullptr,
-                                  const pfb::StridedIn* strided = nullptr) {
-  if (b_hi <= b_lo) return PFB_OK;
-  const int64_t CB = synthesis_chunk_blocks(p, b_hi - b_lo);
-  for (int64_t b0 = b_lo; b0 < b_hi; b0 += CB) {
-    pfb_status st = synthesis_chunk(p, in, in_ps, b0, std::min<int64_t>(CB, b_hi - b0), out, out_ps,
-                                    out_limit, s, row_shift, dada, strided);
+// blocks b in chunks
+static pfb_status synthesis_range(const SynthRows& rows, Blocks b, const SynthOut& out, hipStream_t s) {
+  if (b.hi <= b.lo) return PFB_OK;
+  const int64_t CB = synthesis_chunk_blocks(rows.plan, b.hi - b.lo);
+  for (int64_t b0 = b.lo; b0 < b.hi; b0 += CB) {
+    const pfb_status st = synthesis_chunk(rows, Blocks{b0, std::min(b0 + CB, b.hi)}, out, s);
     if (st != PFB_OK) return st;
   }
   return PFB_OK;
-}
-
-static pfb_status synthesis_run(pfb_synthesis_plan* p, const float2* in, int64_t in_ps, int64_t n_dat,
-                                float2* out, int64_t out_ps, int64_t out_limit, hipStream_t s) {
-  return synthesis_range(p, in, in_ps, 0, synth_blocks(p, n_dat), out, out_ps, out_limit, s);
 }
 
 extern "C" {
@@ -301,10 +308,7 @@ static pfb_status synthesis_validate(const pfb_synthesis_desc* d) {
 }
 
 // Host-side tables of a synthesis plan (double maths, rounded once to float)
-struct SynthHost {
-  int N = 0, nu = 1, de = 1, Nf = 0, Ov = 0, W = 0, keep = 0, L = 0, Lov = 0, Lkeep = 0;
-  int t1_lo = 0, t1_hi = 0, spans = 1, combine = 1;
-  bool deripple = false, identity_perm = true, win_flat = false;
+struct SynthHost : SynthShape {
   std::vector<float> window, cgain, taper, gj;
   std::vector<int> perm;
   std::vector<float2> tw4, tw4s;
@@ -490,24 +494,8 @@ pfb_status pfb_synthesis_plan_create(const pfb_synthesis_desc* d, pfb_synthesis_
   if (const char* v = pfb::knob("PFB_SYNTH_NO_REUSE")) p->no_reuse = std::atoi(v) != 0;
   if (const char* v = pfb::knob("PFB_SYNTH_XCD")) p->xcd = std::atoi(v) != 0;
   if (const char* v = pfb::knob("PFB_RT_CHUNK_BLOCKS")) p->rt_chunk_blocks = std::max(1, std::atoi(v));
-  p->N = h.N;
-  p->nu = h.nu;
-  p->de = h.de;
-  p->Nf = h.Nf;
-  p->Ov = h.Ov;
-  p->spans = h.spans;
-  p->combine = h.combine;
+  static_cast<SynthShape&>(*p) = h;
   p->n_pol = d->n_pol;
-  p->W = h.W;
-  p->keep = h.keep;
-  p->L = h.L;
-  p->Lov = h.Lov;
-  p->Lkeep = h.Lkeep;
-  p->t1_lo = h.t1_lo;
-  p->t1_hi = h.t1_hi;
-  p->deripple = h.deripple;
-  p->identity_perm = h.identity_perm;
-  p->win_flat = h.win_flat;
   hipError_t e = upload(p->window, h.window);
   if (e == hipSuccess) e = upload(p->tw4, h.tw4);
   if (e == hipSuccess) e = upload(p->tw4s, h.tw4s);
@@ -612,78 +600,173 @@ static pfb_status strided_stage(pfb_synthesis_plan* p, const pfb::StridedIn& d, 
   return PFB_OK;
 }
 
-// pfb_synthesis_execute; sec: the rows are a DADA section (device memory) instead of `in`;
-// sv: `in` is read through a strided layout (device memory)
-static pfb_status synthesis_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
-                                 const DadaSection* sec, int64_t n_dat, int64_t sample_offset,
-                                 pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
-                                 int32_t mem, void* stream, const StridedView* sv = nullptr) {
-  if (sec) in = static_cast<const pfb_cf32*>(sec->base);
-  if (!p || (!in && n_dat > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
-  if (sample_offset < 1) return fail(PFB_ERR_INVALID_ARG, "sample_offset is 1-based (>= 1)");
-  if (n_dat < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_dat");
-  if (sv) {
-    const pfb_status st = strided_view_check(p, *sv, n_dat);
-    if (st != PFB_OK) return st;
+// ---- one call, as its entry point was given it
+// The rows: packed cf32 (`in`, pol stride in_ps, in host or device memory), or one of
+// sec: a DADA section (device memory; `in` unused);
+// sv: `in` read through a strided layout (device memory).
+struct SynthIn {
+  const pfb_cf32* in = nullptr;
+  int64_t in_ps = 0;
+  const DadaSection* sec = nullptr;
+  const StridedView* sv = nullptr;
+  int32_t mem = PFB_MEM_DEVICE;
+  const void* base() const { return sec ? sec->base : in; }
+  bool packed() const { return !sec && !sv; }
+};
+
+// The output: nbit 0, cf32 out[pol][t] (pol stride out_ps; cap in samples per polarisation, in
+// the memory the input is in); else a DADA section of that NBIT (cap in bytes), each component
+// to_sample(scale * y)
+struct SynthDst {
+  void* out = nullptr;
+  int64_t out_ps = 0, cap = 0;
+  int64_t* n_out = nullptr;
+  int nbit = 0;
+  float scale = 1.f;
+};
+
+// n rows; sample_offset: 1-based, the stateless calls only
+struct SynthCall {
+  SynthIn in;
+  int64_t n = 0, sample_offset = 1;
+  SynthDst dst;
+  void* stream = nullptr;
+};
+
+static pfb_status capacity_check(const pfb_synthesis_plan* p, const SynthDst& d, int64_t olen) {
+  if (!d.nbit) {
+    if (d.cap < olen)
+      return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld", (long long)d.cap, (long long)olen);
+    return PFB_OK;
   }
+  const int64_t need = olen * p->n_pol * 2 * (d.nbit / 8);
+  if (d.cap < need)
+    return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld bytes", (long long)d.cap, (long long)need);
+  return PFB_OK;
+}
+
+// the pol strides of buffers in device memory cover the data (a section has none)
+static pfb_status stride_check(const pfb_synthesis_plan* p, const SynthCall& c, int64_t olen) {
+  if (c.in.mem == PFB_MEM_DEVICE &&
+      ((c.in.packed() && c.in.in_ps < c.n * p->N) || (!c.dst.nbit && c.dst.out_ps < olen)))
+    return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
+  return PFB_OK;
+}
+
+// The call is under way: its device current, the input reporters start over.  A cf32-output
+// call gets here once its input arguments have passed, before its lengths are known; a to-DADA
+// call only after every check.
+static pfb_status synthesis_begin(pfb_synthesis_plan* p) {
   HIPCHK(hipSetDevice(p->device));
   p->last_dada = PFB_DADA_INPUT_NONE;
   p->last_strided = PFB_STRIDED_INPUT_NONE;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t off = std::min<int64_t>(sample_offset - 1, std::max<int64_t>(n_dat, 0));
-  const int64_t n = n_dat - off;  // in = in(:, :, sample_offset:end)  (polyphase_synthesis.m:99)
-  const int64_t olen = synth_blocks(p, n) * p->Lkeep;
-  if (n_out) *n_out = olen;
-  if (olen == 0) return PFB_OK;
-  if (!out) return fail(PFB_ERR_INVALID_ARG, "null output");
-  if (cap < olen) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld",
-                              (long long)cap, (long long)olen);
-  if (mem == PFB_MEM_DEVICE) {
-    if ((!sec && !sv && in_ps < n_dat * p->N) || out_ps < olen)
-      return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
-    if (sv) {
-      const pfb::StridedIn d{(const float2*)in, sv->ps, sv->rs, sv->cs, n_dat, 0};
-      if (strided_in_place(p))
-        // the blocks start `off` rows into the layout (a negative row shift)
-        return synthesis_range(p, nullptr, 0, 0, synth_blocks(p, n), (float2*)out, out_ps, olen, s, -off, nullptr,
-                               &d);
-      const pfb_status st = strided_stage(p, d, n_dat, s);
-      if (st != PFB_OK) return st;
-      in = reinterpret_cast<const pfb_cf32*>(p->stage_in.p);
-      in_ps = n_dat * p->N;
-    }
-    if (sec) {
-      if (dada_fusable(p, *sec)) {
-        // the blocks start `off` rows into the section (a negative row shift)
-        const pfb::DadaIn d{sec->base, sec->nbit, sec->order == PFB_DADA_LOWCBF, n_dat, 0};
-        return synthesis_range(p, nullptr, 0, 0, synth_blocks(p, n), (float2*)out, out_ps, olen, s, -off, &d);
-      }
-      const pfb_status st = dada_stage(p, *sec, n_dat, s);
-      if (st != PFB_OK) return st;
-      in = reinterpret_cast<const pfb_cf32*>(p->stage_in.p);
-      in_ps = n_dat * p->N;
-    }
-    return synthesis_run(p, (const float2*)in + off * p->N, in_ps, n, (float2*)out, out_ps, olen, s);
+  return PFB_OK;
+}
+
+// the input-side checks both call kinds start with; `what`: the row count's name in the call
+static pfb_status input_check(pfb_synthesis_plan* p, const SynthCall& c, bool stateless, const char* what) {
+  if (!p || (!c.in.base() && c.n > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
+  if (stateless && c.sample_offset < 1) return fail(PFB_ERR_INVALID_ARG, "sample_offset is 1-based (>= 1)");
+  if (c.n < 0) return fail(PFB_ERR_INVALID_ARG, "negative %s", c.dst.nbit ? "row count" : what);
+  if (c.in.sv) {
+    const pfb_status st = strided_view_check(p, *c.in.sv, c.n);
+    if (st != PFB_OK) return st;
   }
-  HIPCHK(p->stage_in.ensure((size_t)p->n_pol * n * p->N * sizeof(float2)));
-  HIPCHK(p->stage_out.ensure((size_t)p->n_pol * olen * sizeof(float2)));
-  HIPCHK(copy_pols(p->stage_in.as<float2>(), n * p->N, (const float2*)in + off * p->N, in_ps,
-                   n * p->N, p->n_pol, hipMemcpyHostToDevice, s));
-  pfb_status st = synthesis_run(p, p->stage_in.as<float2>(), n * p->N, n, p->stage_out.as<float2>(),
-                                olen, olen, s);
+  return c.dst.nbit ? PFB_OK : synthesis_begin(p);
+}
+
+// The lengths of a stateless call: the rows from row `off` on, n of them, olen samples out
+struct SynthLens {
+  int64_t off, n, olen;
+};
+
+// The lengths and the argument checks of a stateless call, with its output counted in the
+// unit of c.dst.  A call that yields nothing checks no more than its input.
+static pfb_status synthesis_check(pfb_synthesis_plan* p, const SynthCall& c, SynthLens& len) {
+  pfb_status st = input_check(p, c, true, "n_dat");
   if (st != PFB_OK) return st;
-  HIPCHK(copy_pols((float2*)out, out_ps, p->stage_out.as<float2>(), olen, olen, p->n_pol,
+  len.off = std::min<int64_t>(c.sample_offset - 1, c.n);
+  len.n = c.n - len.off;  // in = in(:, :, sample_offset:end)  (polyphase_synthesis.m:99)
+  len.olen = synth_blocks(p, len.n) * p->Lkeep;
+  if (c.dst.n_out) *c.dst.n_out = len.olen;
+  if (len.olen == 0) return PFB_OK;
+  if (!c.dst.out) return fail(PFB_ERR_INVALID_ARG, "null output");
+  st = capacity_check(p, c.dst, len.olen);
+  if (st != PFB_OK) return st;
+  return stride_check(p, c, len.olen);
+}
+
+// What an entry point was given -> the rows the launches read: a section or a layout in place
+// where the plan's channel IFFT can (FUSED / IN_PLACE), otherwise unpacked / copied whole into
+// the plan's staging buffer, from where the packed path runs (STAGED).  Row 0 is the input's.
+static pfb_status synth_rows(pfb_synthesis_plan* p, const SynthCall& c, hipStream_t s, SynthRows& rows) {
+  rows = SynthRows::packed(p, (const float2*)c.in.in, c.in.in_ps, c.n);
+  if (c.in.packed()) {
+    if (c.in.mem == PFB_MEM_HOST) rows.copy = hipMemcpyHostToDevice;
+    return PFB_OK;
+  }
+  if (c.in.sv) {
+    const StridedView& v = *c.in.sv;
+    rows.kind = SynthRows::STRIDED;
+    rows.strided = pfb::StridedIn{(const float2*)c.in.in, v.ps, v.rs, v.cs, c.n, 0};
+    if (strided_in_place(p)) return PFB_OK;
+    const pfb_status st = strided_stage(p, rows.strided, c.n, s);
+    if (st != PFB_OK) return st;
+  } else {
+    const DadaSection& sec = *c.in.sec;
+    rows.kind = SynthRows::DADA;
+    rows.dada = pfb::DadaIn{sec.base, sec.nbit, sec.order == PFB_DADA_LOWCBF, c.n, 0};
+    if (dada_fusable(p, sec)) return PFB_OK;
+    const pfb_status st = dada_stage(p, sec, c.n, s);
+    if (st != PFB_OK) return st;
+  }
+  rows = SynthRows::packed(p, p->stage_in.as<float2>(), c.n * p->N, c.n);
+  return PFB_OK;
+}
+
+// pfb_synthesis_execute* once synthesis_check has passed
+static pfb_status synthesis_go(pfb_synthesis_plan* p, const SynthCall& c, const SynthLens& len, const SynthOut& out) {
+  if (len.olen == 0) return PFB_OK;
+  hipStream_t s = (hipStream_t)c.stream;
+  const Blocks all{0, synth_blocks(p, len.n)};
+  SynthRows rows;
+  pfb_status st = synth_rows(p, c, s, rows);
+  if (st != PFB_OK) return st;
+  if (c.in.mem == PFB_MEM_DEVICE) {
+    rows.row0 = len.off;  // the blocks start `off` rows into the buffer, the section, the layout
+    return synthesis_range(rows, all, out, s);
+  }
+  HIPCHK(p->stage_in.ensure((size_t)p->n_pol * len.n * p->N * sizeof(float2)));
+  HIPCHK(p->stage_out.ensure((size_t)p->n_pol * len.olen * sizeof(float2)));
+  HIPCHK(rows.copy_to(len.off, len.n, p->stage_in.as<float2>(), len.n * p->N, s));
+  st = synthesis_range(SynthRows::packed(p, p->stage_in.as<float2>(), len.n * p->N, len.n), all,
+                       SynthOut{p->stage_out.as<float2>(), len.olen, len.olen, {}}, s);
+  if (st != PFB_OK) return st;
+  HIPCHK(copy_pols(out.out, out.out_ps, p->stage_out.as<float2>(), len.olen, len.olen, p->n_pol,
                    hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return PFB_OK;
+}
+
+// the cf32 output of a call that yields olen samples
+static SynthOut cf32_out(const SynthDst& d, int64_t olen) {
+  return SynthOut{static_cast<float2*>(d.out), d.out_ps, olen, {}};
+}
+
+// a cf32-output stateless call
+static pfb_status synthesis_exec(pfb_synthesis_plan* p, const SynthCall& c) {
+  SynthLens len{};
+  const pfb_status st = synthesis_check(p, c, len);
+  if (st != PFB_OK) return st;
+  return cf32_output(p, synthesis_go(p, c, len, cf32_out(c.dst, len.olen)));
 }
 
 pfb_status pfb_synthesis_execute(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
                                  int64_t n_dat, int64_t sample_offset, pfb_cf32* out,
                                  int64_t out_ps, int64_t cap, int64_t* n_out, int32_t mem,
                                  void* stream) {
-  return cf32_output(
-      p, synthesis_exec(p, in, in_ps, nullptr, n_dat, sample_offset, out, out_ps, cap, n_out, mem, stream));
+  return synthesis_exec(p, SynthCall{{in, in_ps, nullptr, nullptr, mem}, n_dat, sample_offset,
+                                     {out, out_ps, cap, n_out}, stream});
 }
 
 pfb_status pfb_synthesis_execute_dada(pfb_synthesis_plan* p, const void* in, int32_t nbit, int32_t ndim,
@@ -692,8 +775,7 @@ pfb_status pfb_synthesis_execute_dada(pfb_synthesis_plan* p, const void* in, int
   const DadaSection sec{in, nbit, ndim, order};
   const pfb_status st = section_check(p, sec, n_dat);
   if (st != PFB_OK) return st;
-  return cf32_output(p, synthesis_exec(p, nullptr, 0, &sec, n_dat, sample_offset, out, out_ps, cap, n_out,
-                                       PFB_MEM_DEVICE, stream));
+  return synthesis_exec(p, SynthCall{{nullptr, 0, &sec}, n_dat, sample_offset, {out, out_ps, cap, n_out}, stream});
 }
 
 int32_t pfb_synthesis_last_dada_input(const pfb_synthesis_plan* p) { return p ? p->last_dada : -1; }
@@ -703,8 +785,8 @@ pfb_status pfb_synthesis_execute_strided(pfb_synthesis_plan* p, const pfb_cf32* 
                                          int64_t sample_offset, pfb_cf32* out, int64_t out_ps, int64_t cap,
                                          int64_t* n_out, void* stream) {
   const StridedView sv{in_ps, in_rs, in_cs, in_cap};
-  return cf32_output(p, synthesis_exec(p, in, in_ps, nullptr, n_dat, sample_offset, out, out_ps, cap, n_out,
-                                       PFB_MEM_DEVICE, stream, &sv));
+  return synthesis_exec(p, SynthCall{{in, in_ps, nullptr, &sv}, n_dat, sample_offset, {out, out_ps, cap, n_out},
+                                     stream});
 }
 
 int32_t pfb_synthesis_last_strided_input(const pfb_synthesis_plan* p) { return p ? p->last_strided : -1; }
@@ -721,14 +803,12 @@ pfb_status pfb_inverse_filterbank_set_sample_offset(pfb_synthesis_plan* p, int64
 // carry starts at input_idat = (output length) nu / (n_chan de) = B keep of the
 // concatenation — not offset by `so`: the next call skips `so` rows of it again, so
 // consecutive calls see the blocks of one continuous run.
-// (sec: the new rows are a DADA section in device memory instead of `in`.  Fusable: the
-// blocks of new rows read it in place, and whatever the cf32 call copies out of `in` — the
-// stitched head, the carry — is unpacked from the section's rows instead.  Otherwise the
-// section is unpacked whole once every check has passed, and the cf32 path runs.)
-// (sv: the new rows lie behind a strided layout in device memory.  The same split: the
-// blocks of new rows read through the layout where the channel IFFT can, the stitched head
-// and the carry are copied out of it by the strided-rows copy kernel; otherwise the rows are
-// copied whole once every check has passed, and the cf32 path runs.)
+// (The new rows as a DADA section or behind a strided layout, in device memory.  Read in
+// place (synth_rows): the blocks of new rows read the section or the layout themselves, and
+// whatever the packed call copies out of `in` — the stitched head, the carry — is unpacked
+// from the section's rows, or copied out of the layout by the strided-rows copy kernel,
+// instead (SynthRows::copy_to).  Otherwise the rows are staged whole once every check has
+// passed, and the packed path runs.)
 // The lengths of a stream call of n_in new rows on the plan's current state
 struct IfbLens {
   int64_t total, so, B, input_idat, buffered, olen;
@@ -753,170 +833,117 @@ static IfbLens ifb_lens(const pfb_synthesis_plan* p, int64_t n_in) {
   return l;
 }
 
-static pfb_status ifb_exec(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps, const DadaSection* sec,
-                           int64_t n_in, pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
-                           int32_t mem, void* stream, const StridedView* sv = nullptr) {
-  if (sec) in = static_cast<const pfb_cf32*>(sec->base);
-  if (!p || (!in && n_in > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
-  if (n_in < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_in");
-  if (sv) {
-    const pfb_status st = strided_view_check(p, *sv, n_in);
-    if (st != PFB_OK) return st;
-  }
-  HIPCHK(hipSetDevice(p->device));
-  p->last_dada = PFB_DADA_INPUT_NONE;
-  p->last_strided = PFB_STRIDED_INPUT_NONE;
-  hipStream_t s = (hipStream_t)stream;
-  const int N = p->N;
-  const hipMemcpyKind kin = mem == PFB_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  const IfbLens len = ifb_lens(p, n_in);
-  const int64_t total = len.total, so = len.so, B = len.B, input_idat = len.input_idat, buffered = len.buffered,
-                olen = len.olen;
-  if (input_idat < 0)
+// The lengths and the argument checks of a stream call, with its output counted in the unit
+// of c.dst (the order differs from synthesis_check's on purpose: it is each call's own)
+static pfb_status ifb_check(pfb_synthesis_plan* p, const SynthCall& c, IfbLens& len) {
+  pfb_status st = input_check(p, c, false, "n_in");
+  if (st != PFB_OK) return st;
+  len = ifb_lens(p, c.n);
+  if (len.input_idat < 0)
     // no complete block and a carry rounded up past the data: InverseFilterBank.m:104-122
     // would index input(:, :, input_idat + 1 : end) before the first sample (its rounding
     // loop never settles); the call is rejected and the object state is left unchanged
     return fail(PFB_ERR_INVALID_ARG,
                 "InverseFilterBank: %lld buffered + %lld new rows hold no complete block and "
                 "round the carry past the data (InverseFilterBank.m:104-122); pass more rows",
-                (long long)p->buffered, (long long)n_in);
-  if (n_out) *n_out = olen;
-  if (olen > cap) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld",
-                              (long long)cap, (long long)olen);
-  if (mem == PFB_MEM_DEVICE && ((!sec && !sv && in_ps < n_in * N) || out_ps < olen))
-    return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
-  if (olen > 0 && !out) return fail(PFB_ERR_INVALID_ARG, "null output");
-  pfb::DadaIn dd{};
-  const pfb::DadaIn* dada = nullptr;
-  pfb::StridedIn sd{};
-  const pfb::StridedIn* strided = nullptr;
-  if (sv) {
-    sd = pfb::StridedIn{(const float2*)in, sv->ps, sv->rs, sv->cs, n_in, 0};
-    if (strided_in_place(p)) {
-      strided = &sd;
-      in = nullptr;
-    } else {
-      const pfb_status st = strided_stage(p, sd, n_in, s);
-      if (st != PFB_OK) return st;
-      in = reinterpret_cast<const pfb_cf32*>(p->stage_in.p);
-      in_ps = n_in * N;
-    }
+                (long long)p->buffered, (long long)c.n);
+  if (c.dst.n_out) *c.dst.n_out = len.olen;
+  st = capacity_check(p, c.dst, len.olen);
+  if (st != PFB_OK) return st;
+  st = stride_check(p, c, len.olen);
+  if (st != PFB_OK) return st;
+  if (len.olen > 0 && !c.dst.out) return fail(PFB_ERR_INVALID_ARG, "null output");
+  return PFB_OK;
+}
+
+// The next call's carry: rows [r, r + n) of `rows` into the plan's carry buffer, n <= 0 none
+// (twin of the analysis' fb_carry)
+static pfb_status ifb_store_carry(const SynthRows& rows, int64_t r, int64_t n, hipStream_t s) {
+  pfb_synthesis_plan* p = rows.plan;
+  if (n > 0) {
+    HIPCHK(p->carry.ensure((size_t)p->n_pol * n * p->N * sizeof(float2)));
+    HIPCHK(rows.copy_to(r, n, p->carry.as<float2>(), n * p->N, s));
   }
-  if (sec) {
-    if (dada_fusable(p, *sec)) {
-      dd = pfb::DadaIn{sec->base, sec->nbit, sec->order == PFB_DADA_LOWCBF, n_in, 0};
-      dada = &dd;
-      in = nullptr;
-    } else {
-      const pfb_status st = dada_stage(p, *sec, n_in, s);
-      if (st != PFB_OK) return st;
-      in = reinterpret_cast<const pfb_cf32*>(p->stage_in.p);
-      in_ps = n_in * N;
-    }
-  }
-  // rows [row0, row0 + n) of the new input -> dst[pol][0, n N)
-  auto rows_to = [&](float2* dst, int64_t dps, int64_t row0, int64_t n) -> hipError_t {
-    if (dada) {
-      pfb::DadaIn d = dd;
-      d.t0 = row0;
-      if (p->last_dada == PFB_DADA_INPUT_NONE) p->last_dada = PFB_DADA_INPUT_STAGED;
-      return pfb::launch_dada_unpack_rows(d, n, N, p->n_pol, dst, dps, s);
-    }
-    if (strided) {
-      pfb::StridedIn d = sd;
-      d.t0 = row0;
-      if (p->last_strided == PFB_STRIDED_INPUT_NONE) p->last_strided = PFB_STRIDED_INPUT_STAGED;
-      return pfb::launch_strided_rows_copy(d, n, N, p->n_pol, dst, dps, s);
-    }
-    return copy_pols(dst, dps, (const float2*)in + row0 * N, in_ps, n * N, p->n_pol, kin, s);
-  };
-  {
-    // Carry without the concatenation copy: blocks whose rows start at or after the
-    // carried Bc rows read the new input in place (row shift Bc - so), the first ones a
-    // small stitched buffer; same blocks, same kernels as the concatenated run.
-    const int64_t Bc = p->buffered;
-    static const bool no_split = pfb::knob("PFB_FB_NO_SPLIT") != nullptr;  // A/B
-    if (!no_split && mem == PFB_MEM_DEVICE && Bc > 0 && !p->has_spectral && input_idat >= Bc) {
-      if (olen > 0) {
-        // first block starting at or after row Bc of the concatenation: so + b keep >= Bc
-        const int64_t b_s = std::min(B, std::max<int64_t>(0, (Bc - so + p->keep - 1) / p->keep));
-        if (b_s > 0) {
-          const int64_t L = std::min(total, so + (b_s - 1) * p->keep + p->Nf);
-          HIPCHK(p->work.ensure((size_t)p->n_pol * L * N * sizeof(float2)));
-          float2* wk = p->work.as<float2>();
-          HIPCHK(copy_pols(wk, L * N, p->carry.as<float2>(), Bc * N, std::min(Bc, L) * N, p->n_pol,
-                           hipMemcpyDeviceToDevice, s));
-          if (L > Bc) HIPCHK(rows_to(wk + Bc * N, L * N, 0, L - Bc));
-          pfb_status st = synthesis_range(p, wk, L * N, 0, b_s, (float2*)out, out_ps, olen, s, -so);
-          if (st != PFB_OK) return st;
-        }
-        pfb_status st = synthesis_range(p, (const float2*)in, in_ps, b_s, B, (float2*)out, out_ps, olen, s,
-                                        Bc - so, dada, strided);
+  p->buffered = std::max<int64_t>(n, 0);
+  return PFB_OK;
+}
+
+// pfb_inverse_filterbank_execute* once ifb_check has passed
+static pfb_status ifb_go(pfb_synthesis_plan* p, const SynthCall& c, const IfbLens& len, const SynthOut& out) {
+  hipStream_t s = (hipStream_t)c.stream;
+  const int N = p->N;
+  const bool device = c.in.mem == PFB_MEM_DEVICE, to_host = c.in.mem == PFB_MEM_HOST;
+  const int64_t Bc = p->buffered;
+  SynthRows rows;  // the new rows
+  pfb_status st = synth_rows(p, c, s, rows);
+  if (st != PFB_OK) return st;
+  // Carry without the concatenation copy: blocks whose rows start at or after the carried
+  // Bc rows read the new rows in place (call row 0 is their row so - Bc), the first ones a
+  // small stitched buffer; same blocks, same kernels as the concatenated run.
+  static const bool no_split = pfb::knob("PFB_FB_NO_SPLIT") != nullptr;  // A/B
+  if (!no_split && device && Bc > 0 && !p->has_spectral && len.input_idat >= Bc) {
+    if (len.olen > 0) {
+      // first block starting at or after row Bc of the concatenation: so + b keep >= Bc
+      const int64_t b_s = std::min(len.B, std::max<int64_t>(0, (Bc - len.so + p->keep - 1) / p->keep));
+      if (b_s > 0) {
+        const int64_t L = std::min(len.total, len.so + (b_s - 1) * p->keep + p->Nf);
+        HIPCHK(p->work.ensure((size_t)p->n_pol * L * N * sizeof(float2)));
+        float2* wk = p->work.as<float2>();
+        HIPCHK(copy_pols(wk, L * N, p->carry.as<float2>(), Bc * N, std::min(Bc, L) * N, p->n_pol,
+                         hipMemcpyDeviceToDevice, s));
+        if (L > Bc) HIPCHK(rows.copy_to(0, L - Bc, wk + Bc * N, L * N, s));
+        SynthRows head = SynthRows::packed(p, wk, L * N, L);
+        head.row0 = len.so;
+        st = synthesis_range(head, Blocks{0, b_s}, out, s);
         if (st != PFB_OK) return st;
       }
-      if (buffered > 0) {
-        HIPCHK(p->carry.ensure((size_t)p->n_pol * buffered * N * sizeof(float2)));
-        HIPCHK(rows_to(p->carry.as<float2>(), buffered * N, input_idat - Bc, buffered));
-      }
-      p->buffered = std::max<int64_t>(buffered, 0);
-      return PFB_OK;
+      rows.row0 = len.so - Bc;
+      st = synthesis_range(rows, Blocks{b_s, len.B}, out, s);
+      if (st != PFB_OK) return st;
     }
+    return ifb_store_carry(rows, len.input_idat - Bc, len.buffered, s);
   }
-  // input = cat(3, input_buffer, input); read in place when nothing is buffered
-  const float2* w;
-  int64_t wps;
-  if (p->buffered == 0 && mem == PFB_MEM_DEVICE) {
-    w = (const float2*)in;
-    wps = in_ps;
-    if (dada || strided) {
-      // nothing carried: every block reads the section (the layout) in place, the carry is
-      // its unpacked (copied) tail
-      if (olen > 0) {
-        pfb_status st = synthesis_range(p, nullptr, 0, 0, B, (float2*)out, out_ps, olen, s, -so, dada, strided);
-        if (st != PFB_OK) return st;
-      }
-      if (buffered > 0) {
-        HIPCHK(p->carry.ensure((size_t)p->n_pol * buffered * N * sizeof(float2)));
-        HIPCHK(rows_to(p->carry.as<float2>(), buffered * N, input_idat, buffered));
-      }
-      p->buffered = std::max<int64_t>(buffered, 0);
-      return PFB_OK;
-    }
-  } else {
-    HIPCHK(p->work.ensure((size_t)p->n_pol * std::max<int64_t>(total, 1) * N * sizeof(float2)));
+  // input = cat(3, input_buffer, input); the new rows themselves when nothing is buffered
+  // (every block reads them where they lie, the carry is their copied or unpacked tail)
+  SynthRows cat = rows;
+  if (Bc != 0 || !device) {
+    HIPCHK(p->work.ensure((size_t)p->n_pol * std::max<int64_t>(len.total, 1) * N * sizeof(float2)));
     float2* wk = p->work.as<float2>();
-    HIPCHK(copy_pols(wk, total * N, p->carry.as<float2>(), p->buffered * N, p->buffered * N, p->n_pol,
-                     hipMemcpyDeviceToDevice, s));
-    HIPCHK(rows_to(wk + p->buffered * N, total * N, 0, n_in));
-    w = wk;
-    wps = total * N;
+    HIPCHK(copy_pols(wk, len.total * N, p->carry.as<float2>(), Bc * N, Bc * N, p->n_pol, hipMemcpyDeviceToDevice, s));
+    HIPCHK(rows.copy_to(0, c.n, wk + Bc * N, len.total * N, s));
+    cat = SynthRows::packed(p, wk, len.total * N, len.total);
   }
-  if (olen > 0) {
-    if (mem == PFB_MEM_HOST) {
-      HIPCHK(p->stage_out.ensure((size_t)p->n_pol * olen * sizeof(float2)));
-      pfb_status st = synthesis_range(p, w, wps, 0, B, p->stage_out.as<float2>(), olen, olen, s, -so);
+  cat.row0 = len.so;
+  if (len.olen > 0) {
+    if (to_host) {
+      HIPCHK(p->stage_out.ensure((size_t)p->n_pol * len.olen * sizeof(float2)));
+      st = synthesis_range(cat, Blocks{0, len.B}, SynthOut{p->stage_out.as<float2>(), len.olen, len.olen, {}}, s);
       if (st != PFB_OK) return st;
-      HIPCHK(copy_pols((float2*)out, out_ps, p->stage_out.as<float2>(), olen, olen, p->n_pol,
+      HIPCHK(copy_pols(out.out, out.out_ps, p->stage_out.as<float2>(), len.olen, len.olen, p->n_pol,
                        hipMemcpyDeviceToHost, s));
     } else {
-      pfb_status st = synthesis_range(p, w, wps, 0, B, (float2*)out, out_ps, olen, s, -so);
+      st = synthesis_range(cat, Blocks{0, len.B}, out, s);
       if (st != PFB_OK) return st;
     }
   }
-  if (buffered > 0) {
-    HIPCHK(p->carry.ensure((size_t)p->n_pol * buffered * N * sizeof(float2)));
-    HIPCHK(copy_pols(p->carry.as<float2>(), buffered * N, w + input_idat * N, wps, buffered * N,
-                     p->n_pol, hipMemcpyDeviceToDevice, s));
-  }
-  p->buffered = std::max<int64_t>(buffered, 0);
-  if (mem == PFB_MEM_HOST) HIPCHK(hipStreamSynchronize(s));
+  st = ifb_store_carry(cat, len.input_idat, len.buffered, s);
+  if (st != PFB_OK) return st;
+  if (to_host) HIPCHK(hipStreamSynchronize(s));
   return PFB_OK;
+}
+
+// a cf32-output stream call
+static pfb_status ifb_exec(pfb_synthesis_plan* p, const SynthCall& c) {
+  IfbLens len{};
+  const pfb_status st = ifb_check(p, c, len);
+  if (st != PFB_OK) return st;
+  return cf32_output(p, ifb_go(p, c, len, cf32_out(c.dst, len.olen)));
 }
 
 pfb_status pfb_inverse_filterbank_execute(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
                                           int64_t n_in, pfb_cf32* out, int64_t out_ps, int64_t cap,
                                           int64_t* n_out, int32_t mem, void* stream) {
-  return cf32_output(p, ifb_exec(p, in, in_ps, nullptr, n_in, out, out_ps, cap, n_out, mem, stream));
+  return ifb_exec(p, SynthCall{{in, in_ps, nullptr, nullptr, mem}, n_in, 1, {out, out_ps, cap, n_out}, stream});
 }
 
 pfb_status pfb_inverse_filterbank_execute_dada(pfb_synthesis_plan* p, const void* in, int32_t nbit,
@@ -925,7 +952,7 @@ pfb_status pfb_inverse_filterbank_execute_dada(pfb_synthesis_plan* p, const void
   const DadaSection sec{in, nbit, ndim, order};
   const pfb_status st = section_check(p, sec, n_in);
   if (st != PFB_OK) return st;
-  return cf32_output(p, ifb_exec(p, nullptr, 0, &sec, n_in, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream));
+  return ifb_exec(p, SynthCall{{nullptr, 0, &sec}, n_in, 1, {out, out_ps, cap, n_out}, stream});
 }
 
 pfb_status pfb_inverse_filterbank_execute_strided(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
@@ -933,7 +960,7 @@ pfb_status pfb_inverse_filterbank_execute_strided(pfb_synthesis_plan* p, const p
                                                   pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
                                                   void* stream) {
   const StridedView sv{in_ps, in_rs, in_cs, in_cap};
-  return cf32_output(p, ifb_exec(p, in, in_ps, nullptr, n_in, out, out_ps, cap, n_out, PFB_MEM_DEVICE, stream, &sv));
+  return ifb_exec(p, SynthCall{{in, in_ps, nullptr, &sv}, n_in, 1, {out, out_ps, cap, n_out}, stream});
 }
 
 }  // extern "C"
@@ -958,78 +985,41 @@ bool pfb::host::synthesis_dada_out_fusable(const pfb_synthesis_plan* p, const vo
 
 extern "C" {
 
-// The to-DADA calls (pfb_api.h): every check here — the callee's own, in its order, among
-// them — before the callee launches or changes the stream state; then FUSED — the plan's block
-// launches store the section (pfb_synthesis_plan::dout) — or STAGED — the cf32 path into the
-// plan's buffer and the scaled pack launch.
-static pfb_status synthesis_to_dada(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
-                                    const DadaSection* sec, int64_t n, int64_t sample_offset, void* out,
-                                    int32_t nbit, float scale, int64_t cap_bytes, int64_t* n_out, void* stream,
-                                    bool stream_call) {
+// The to-DADA calls (pfb_api.h): every check — the section's own, then the corresponding
+// cf32-output call's in its order (synthesis_check / ifb_check, the capacity in bytes) — before
+// anything is launched or the stream state changes; then FUSED — the call's block launches
+// store the section (SynthOut::dada) — or STAGED — the cf32 path into the plan's buffer and the
+// scaled pack launch.
+static pfb_status synthesis_to_dada(pfb_synthesis_plan* p, const SynthCall& c, bool stream_call) {
+  const SynthDst& d = c.dst;
   if (!p) return fail(PFB_ERR_INVALID_ARG, "null plan");
-  if (nbit != 8 && nbit != 16 && nbit != 32 && nbit != 64)
+  if (d.nbit != 8 && d.nbit != 16 && d.nbit != 32 && d.nbit != 64)
     return fail(PFB_ERR_INVALID_ARG, "output NBIT must be 8, 16, 32 or 64");
-  if (!std::isfinite(scale)) return fail(PFB_ERR_INVALID_ARG, "output scale is not finite");
-  if (reinterpret_cast<uintptr_t>(out) % (size_t)(nbit / 8) != 0)
+  if (!std::isfinite(d.scale)) return fail(PFB_ERR_INVALID_ARG, "output scale is not finite");
+  if (reinterpret_cast<uintptr_t>(d.out) % (size_t)(d.nbit / 8) != 0)
     return fail(PFB_ERR_INVALID_ARG, "output section not aligned to its NBIT");
-  // the input-side conditions of the corresponding cf32-output call
-  if (sec) {
-    const pfb_status st = section_check(p, *sec, n);
+  if (c.in.sec) {
+    const pfb_status st = section_check(p, *c.in.sec, c.n);
     if (st != PFB_OK) return st;
   }
-  if (!(sec ? sec->base : (const void*)in) && n > 0) return fail(PFB_ERR_INVALID_ARG, "null argument");
-  if (!stream_call && sample_offset < 1) return fail(PFB_ERR_INVALID_ARG, "sample_offset is 1-based (>= 1)");
-  if (n < 0) return fail(PFB_ERR_INVALID_ARG, "negative row count");
-  int64_t olen;
-  if (stream_call) {
-    const IfbLens len = ifb_lens(p, n);
-    if (len.input_idat < 0)
-      return fail(PFB_ERR_INVALID_ARG,
-                  "InverseFilterBank: %lld buffered + %lld new rows hold no complete block and "
-                  "round the carry past the data (InverseFilterBank.m:104-122); pass more rows",
-                  (long long)p->buffered, (long long)n);
-    olen = len.olen;
-  } else {
-    const int64_t off = std::min<int64_t>(sample_offset - 1, n);
-    olen = synth_blocks(p, n - off) * p->Lkeep;
-  }
-  if (n_out) *n_out = olen;
-  const int64_t need = olen * p->n_pol * 2 * (nbit / 8);
-  if (stream_call) {  // (pfb_inverse_filterbank_execute's order)
-    if (cap_bytes < need)
-      return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld bytes", (long long)cap_bytes,
-                  (long long)need);
-    if (!sec && in_ps < n * p->N) return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
-    if (olen > 0 && !out) return fail(PFB_ERR_INVALID_ARG, "null output");
-  } else if (olen > 0) {  // (pfb_synthesis_execute's; a call that yields nothing checks no more)
-    if (!out) return fail(PFB_ERR_INVALID_ARG, "null output");
-    if (cap_bytes < need)
-      return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld bytes", (long long)cap_bytes,
-                  (long long)need);
-    if (!sec && in_ps < n * p->N) return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
-  }
-  HIPCHK(hipSetDevice(p->device));
-  const bool fused = synthesis_dada_out_fusable(p, out, nbit);
-  pfb_cf32* o;
-  if (fused) {
-    // (`out` stands in for the cf32 buffer in the callee's null, capacity and stride checks;
-    // the block launches write through the plan's dout only)
-    o = static_cast<pfb_cf32*>(out);
-    p->dout = out;
-    p->dout_nbit = nbit;
-    p->dout_scale = scale;
-  } else {
+  SynthLens len{};
+  IfbLens ilen{};
+  pfb_status st = stream_call ? ifb_check(p, c, ilen) : synthesis_check(p, c, len);
+  if (st != PFB_OK) return st;
+  const int64_t olen = stream_call ? ilen.olen : len.olen;
+  st = synthesis_begin(p);
+  if (st != PFB_OK) return st;
+  const bool fused = synthesis_dada_out_fusable(p, d.out, d.nbit);
+  SynthOut o{nullptr, olen, olen, SynthDada{d.out, d.nbit, d.scale}};
+  if (!fused) {
     HIPCHK(p->stage_out.ensure((size_t)p->n_pol * std::max<int64_t>(olen, 1) * sizeof(float2)));
-    o = p->stage_out.as<pfb_cf32>();
+    o = SynthOut{p->stage_out.as<float2>(), olen, olen, {}};
   }
-  const pfb_status st =
-      stream_call ? ifb_exec(p, in, in_ps, sec, n, o, olen, olen, n_out, PFB_MEM_DEVICE, stream)
-                  : synthesis_exec(p, in, in_ps, sec, n, sample_offset, o, olen, olen, n_out, PFB_MEM_DEVICE, stream);
-  p->dout = nullptr;
+  st = stream_call ? ifb_go(p, c, ilen, o) : synthesis_go(p, c, len, o);
   if (st != PFB_OK) return st;
   if (!fused && olen > 0)
-    HIPCHK(pfb::launch_dada_pack_scaled(p->stage_out.as<float2>(), olen, olen, 1, p->n_pol, out, nbit, scale,
-                                        (hipStream_t)stream));
+    HIPCHK(pfb::launch_dada_pack_scaled(p->stage_out.as<float2>(), olen, olen, 1, p->n_pol, d.out, d.nbit, d.scale,
+                                        (hipStream_t)c.stream));
   p->last_dada_out = fused ? PFB_DADA_OUTPUT_FUSED : PFB_DADA_OUTPUT_STAGED;
   return PFB_OK;
 }
@@ -1037,14 +1027,15 @@ static pfb_status synthesis_to_dada(pfb_synthesis_plan* p, const pfb_cf32* in, i
 pfb_status pfb_synthesis_execute_to_dada(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps, int64_t n_dat,
                                          int64_t sample_offset, void* out, int32_t out_nbit, float out_scale,
                                          int64_t cap_bytes, int64_t* n_out, void* stream) {
-  return synthesis_to_dada(p, in, in_ps, nullptr, n_dat, sample_offset, out, out_nbit, out_scale, cap_bytes, n_out,
-                           stream, false);
+  return synthesis_to_dada(
+      p, SynthCall{{in, in_ps}, n_dat, sample_offset, {out, 0, cap_bytes, n_out, out_nbit, out_scale}, stream}, false);
 }
 
 pfb_status pfb_inverse_filterbank_execute_to_dada(pfb_synthesis_plan* p, const pfb_cf32* in, int64_t in_ps,
                                                   int64_t n_in, void* out, int32_t out_nbit, float out_scale,
                                                   int64_t cap_bytes, int64_t* n_out, void* stream) {
-  return synthesis_to_dada(p, in, in_ps, nullptr, n_in, 1, out, out_nbit, out_scale, cap_bytes, n_out, stream, true);
+  return synthesis_to_dada(
+      p, SynthCall{{in, in_ps}, n_in, 1, {out, 0, cap_bytes, n_out, out_nbit, out_scale}, stream}, true);
 }
 
 pfb_status pfb_synthesis_execute_dada_to_dada(pfb_synthesis_plan* p, const void* in, int32_t nbit, int32_t ndim,
@@ -1052,8 +1043,9 @@ pfb_status pfb_synthesis_execute_dada_to_dada(pfb_synthesis_plan* p, const void*
                                               int32_t out_nbit, float out_scale, int64_t cap_bytes, int64_t* n_out,
                                               void* stream) {
   const DadaSection sec{in, nbit, ndim, order};
-  return synthesis_to_dada(p, nullptr, 0, &sec, n_dat, sample_offset, out, out_nbit, out_scale, cap_bytes, n_out,
-                           stream, false);
+  return synthesis_to_dada(
+      p, SynthCall{{nullptr, 0, &sec}, n_dat, sample_offset, {out, 0, cap_bytes, n_out, out_nbit, out_scale}, stream},
+      false);
 }
 
 pfb_status pfb_inverse_filterbank_execute_dada_to_dada(pfb_synthesis_plan* p, const void* in, int32_t nbit,
@@ -1061,7 +1053,8 @@ pfb_status pfb_inverse_filterbank_execute_dada_to_dada(pfb_synthesis_plan* p, co
                                                        int32_t out_nbit, float out_scale, int64_t cap_bytes,
                                                        int64_t* n_out, void* stream) {
   const DadaSection sec{in, nbit, ndim, order};
-  return synthesis_to_dada(p, nullptr, 0, &sec, n_in, 1, out, out_nbit, out_scale, cap_bytes, n_out, stream, true);
+  return synthesis_to_dada(
+      p, SynthCall{{nullptr, 0, &sec}, n_in, 1, {out, 0, cap_bytes, n_out, out_nbit, out_scale}, stream}, true);
 }
 
 int32_t pfb_synthesis_last_dada_output(const pfb_synthesis_plan* p) { return p ? p->last_dada_out : -1; }

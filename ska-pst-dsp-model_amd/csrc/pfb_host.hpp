@@ -144,6 +144,16 @@ struct ProfScope {
   }
 };
 
+// The scalar shape of a synthesis: what the descriptor fixes before any table or buffer
+// exists.  The host-side tables (SynthHost) and the plan both derive from it.
+struct SynthShape {
+  int N = 0, nu = 1, de = 1, Nf = 0, Ov = 0, spans = 1, combine = 1;
+  int W = 0, keep = 0, L = 0, Lov = 0, Lkeep = 0, t1_lo = 0, t1_hi = 0;
+  bool deripple = false;
+  bool identity_perm = true;
+  bool win_flat = false;  // SynthBlockArgs::win_flat
+};
+
 }  // namespace pfb::host
 
 // ====================================================================== the plans
@@ -174,30 +184,21 @@ struct pfb_analysis_plan {
   std::vector<hipEvent_t> events;
 };
 
-struct pfb_synthesis_plan {
+struct pfb_synthesis_plan : pfb::host::SynthShape {
   using DevBuf = pfb::host::DevBuf;
   int device = 0;
-  int N = 0, nu = 1, de = 1, Nf = 0, Ov = 0, spans = 1, combine = 1, n_pol = 1;
-  int W = 0, keep = 0, L = 0, Lov = 0, Lkeep = 0, t1_lo = 0, t1_hi = 0;
-  bool deripple = false;
+  int n_pol = 1;
   int chunk_blocks = 0;
   int stage1 = PFB_STAGE1_AUTO;  // pfb_synthesis_set_stage1_rows
   int last_stage1 = 0;           // pfb_synthesis_last_stage1_rows: where the last launch got its rows
   int last_dada = PFB_DADA_INPUT_NONE;  // pfb_synthesis_last_dada_input
   int last_strided = PFB_STRIDED_INPUT_NONE;  // pfb_synthesis_last_strided_input
   int last_dada_out = PFB_DADA_OUTPUT_NONE;   // pfb_synthesis_last_dada_output
-  // set for the duration of a FUSED to-DADA call (synthesis_to_dada): every block launch of the
-  // call stores into this section instead of its cf32 output (SynthBlockArgs::dout)
-  void* dout = nullptr;
-  int dout_nbit = 0;
-  float dout_scale = 1.f;
   int rt_chunk_blocks = 64;  // round-trip pipeline chunk (PFB_RT_CHUNK_BLOCKS)
   int timing_mask = 0;  // PFB_TIMING_MASK (timing experiments; results invalid when set)
   int ranges = -1;  // PFB_SYNTH_RANGES: 0 one workgroup per block, -1 persistent auto, >0 persistent
   int no_reuse = 0;  // PFB_SYNTH_NO_REUSE: re-read the overlap rows (A/B measurement only)
   int xcd = 1;       // PFB_SYNTH_XCD=0: plain workgroup order (A/B measurement only)
-  bool identity_perm = true;
-  bool win_flat = false;  // SynthBlockArgs::win_flat
   bool has_cgain = false;
   bool has_spectral = false;  // non-identity spectral taper: pfb_spectral.hip path
   DevBuf window, tw4, tw4s, twN, twNf, twW, perm, cgain;
@@ -321,22 +322,79 @@ struct FirSrc {
   int nu, de, pe;
 };
 
+// Where the block launches of a call store: the cf32 series out[pol][t] (pol stride out_ps), or
+// the DADA section `dada` instead (TFP, NDIM 2, NBIT 8 / 16 / 32, aligned to a complex sample,
+// each component to_sample(scale * y): SynthBlockArgs::dout; synthesis_dada_out_fusable plans
+// only), and `out` stays null.  Either way no sample at or past out_limit is stored.
+struct SynthDada {
+  void* base = nullptr;
+  int nbit = 0;
+  float scale = 1.f;
+};
+struct SynthOut {
+  float2* out = nullptr;
+  int64_t out_ps = 0, out_limit = 0;
+  SynthDada dada;
+};
+
 // One block-kernel launch over blocks [b0, b0 + nb); Z row 0 is channelised row b0 * keep, in
 // runs of zblk rows; fir: the rows are recomputed from the input series instead
 struct SynthLaunch {
   const float2* Z = nullptr;
   int64_t z_ps = 0, b0 = 0, nb = 0;
-  float2* out = nullptr;
-  int64_t out_ps = 0, out_limit = 0;
+  SynthOut o;
   int zblk = 0;
   const FirSrc* fir = nullptr;
 };
 
+// The channelised rows a synthesis call reads, wherever they lie.  Every row index the two
+// operations take is a row of this source; row0 says where the call's rows sit in it.
+struct SynthRows {
+  enum Kind { PACKED, DADA, STRIDED };
+  pfb_synthesis_plan* plan = nullptr;
+  Kind kind = PACKED;
+  // PACKED: cf32 [pol][row][chan] from `base`, pol stride ps; copy: how a copy out of it goes
+  // (HostToDevice for a caller's host buffer)
+  const float2* base = nullptr;
+  int64_t ps = 0;
+  hipMemcpyKind copy = hipMemcpyDeviceToDevice;
+  // DADA: a section the channel IFFT reads in place (dada_fusable); STRIDED: rows behind a
+  // strided layout it reads through (strided_in_place).  Their t0 is set launch by launch.
+  pfb::DadaIn dada{};
+  pfb::StridedIn strided{};
+  int64_t rows = 0;  // rows available from row 0 of the source
+  // The row of the source that is the call's row 0: block b reads from row row0 + b keep on.
+  // Positive: the call starts that many rows in (a sample offset).  Negative: the call's first
+  // -row0 rows are not in this source (a stream call whose carried rows are not in front of the
+  // new ones), and only blocks that start at or after them may be run on it.
+  int64_t row0 = 0;
+
+  static SynthRows packed(pfb_synthesis_plan* p, const float2* base, int64_t ps, int64_t rows) {
+    SynthRows r;
+    r.plan = p;
+    r.base = base;
+    r.ps = ps;
+    r.rows = rows;
+    return r;
+  }
+  // The input side of `c` for rows [r, r + n): the launch reads them in place (a section or a
+  // layout must hold them all; the plan's last_dada / last_strided then report FUSED /
+  // IN_PLACE).  `c` points into this object.
+  pfb_status chan_in(int64_t r, int64_t n, pfb::ChanIfftArgs& c);
+  // Rows [r, r + n) -> dst[pol][0, n N), pol stride dps: a copy, the unpack kernel or the
+  // strided-rows copy kernel (last_dada / last_strided report STAGED unless a launch of the
+  // call has read in place already)
+  hipError_t copy_to(int64_t r, int64_t n, float2* dst, int64_t dps, hipStream_t s) const;
+};
+
+// blocks [lo, hi) of a call
+struct Blocks {
+  int64_t lo, hi;
+};
+
 pfb::SynthBlockArgs synth_args(const pfb_synthesis_plan* p, const SynthLaunch& l);
 pfb_status synthesis_blocks(pfb_synthesis_plan* p, const SynthLaunch& l, hipStream_t s);
-pfb_status synthesis_chunk(pfb_synthesis_plan* p, const float2* in, int64_t in_ps, int64_t b0, int64_t nb,
-                           float2* out, int64_t out_ps, int64_t out_limit, hipStream_t s, int64_t row_shift = 0,
-                           const pfb::DadaIn* dada = nullptr, const pfb::StridedIn* strided = nullptr);
+pfb_status synthesis_chunk(SynthRows rows, Blocks b, const SynthOut& out, hipStream_t s);
 int64_t synth_blocks(const pfb_synthesis_plan* p, int64_t n_dat);
 void zkey_clear(pfb_synthesis_plan* p);
 bool synthesis_dada_out_fusable(const pfb_synthesis_plan* p, const void* out, int nbit);

@@ -1,5 +1,5 @@
 """A plain-integer restatement of the two stream-object state machines of the C ABI:
-``filterbank_exec`` (pfb_filterbank_execute / _strided / _dada) and ``ifb_exec``
+``filterbank_exec`` (pfb_filterbank_execute / _strided / _dada) and ``ifb_check`` / ``ifb_go``
 (pfb_inverse_filterbank_execute / _strided / _dada) in
 ska-pst-dsp-model_amd/csrc/pfb_api_analysis.hip and pfb_api_synthesis.hip.
 
@@ -209,7 +209,7 @@ SynthesisCall = namedtuple(
 
 
 def synthesis_call(shape, Bc, n_in, entry="packed", spectral=False):
-    """One ifb_exec call on a state of Bc buffered rows (its lengths: ifb_lens).  ``rows`` is the output
+    """One stream call (ifb_check, ifb_go) on a state of Bc buffered rows (its lengths: ifb_lens).  ``rows`` is the output
     length in samples; a rejected call leaves the carry as it was."""
     assert entry in SYNTHESIS_ENTRIES and n_in >= 0 and Bc >= 0
     total = Bc + n_in  # ifb_lens
@@ -229,16 +229,16 @@ def synthesis_call(shape, Bc, n_in, entry="packed", spectral=False):
         flags.add("rounded_carry")
     if n_in == 0 and Bc > 0:
         flags.add("zero_len_call")
-    if input_idat < 0:  # ifb_exec: the call is rejected
+    if input_idat < 0:  # ifb_check: the call is rejected
         flags.discard("rounded_carry")
         return SynthesisCall(n_in, entry, Bc, B, input_idat, 0, full, Bc, "rejected", 0, 0,
                              frozenset(flags | {"rejected"}))
     if olen < full:
         flags.add("olen_lt_full")
     b_s = stitched_new = 0
-    if entry != "host" and Bc > 0 and not spectral and input_idat >= Bc:  # ifb_exec, split path
+    if entry != "host" and Bc > 0 and not spectral and input_idat >= Bc:  # ifb_go, split path
         if olen > 0:
-            # first block that starts at or after row Bc of the concatenation (ifb_exec, split path: b_s)
+            # first block that starts at or after row Bc of the concatenation (ifb_go, split path: b_s)
             b_s = min(B, max(0, (Bc - so + shape.keep - 1) // shape.keep))
             if b_s > 0:
                 L = min(total, so + (b_s - 1) * shape.keep + shape.Nf)  # the stitched buffer's rows
@@ -246,7 +246,7 @@ def synthesis_call(shape, Bc, n_in, entry="packed", spectral=False):
         path = "split(%d, %d)" % (b_s, B)
         if input_idat == Bc:
             flags.add("idat_eq_carry")
-    elif Bc == 0 and entry != "host":  # ifb_exec, in-place branch
+    elif Bc == 0 and entry != "host":  # ifb_go, nothing buffered
         path = "in_place"
     else:
         path = "concat"
@@ -274,10 +274,10 @@ def synthesis_diag(rec, reads_in_place=True):
     """(last_strided_input, last_dada_input) after an ACCEPTED call (include/pfb_api.h:354-356,
     437-439).  ``reads_in_place``: the plan's channel IFFT can read the layout / the section
     itself (strided_in_place / dada_fusable); otherwise every strided or DADA call
-    is staged whole (ifb_exec: strided_stage, dada_stage).  In place where any block of new rows is read through the
+    is staged whole (synth_rows: strided_stage, dada_stage).  In place where any block of new rows is read through the
     entry (blocks [b_s, B) of the split path, every block with nothing buffered); staged where
-    only the copy kernel touched the new rows (stitched head, carry, concatenation: ifb_exec's
-    rows_to); none where nothing of the entry was read."""
+    only the copy kernel touched the new rows (stitched head, carry, concatenation:
+    SynthRows::copy_to); none where nothing of the entry was read."""
     if rec.entry not in ("strided", "dada"):
         return "none", "none"
     if not reads_in_place:
@@ -285,7 +285,7 @@ def synthesis_diag(rec, reads_in_place=True):
     elif rec.path == "in_place":
         d = "in_place" if rec.rows > 0 else "staged" if rec.carry_after > 0 else "none"
     elif rec.path == "concat":
-        d = "staged"  # rows_to runs for every concatenation (ifb_exec)
+        d = "staged"  # SynthRows::copy_to runs for every concatenation (ifb_go)
     else:
         if rec.rows > 0 and rec.b_s < rec.blocks:
             d = "in_place"
@@ -296,6 +296,20 @@ def synthesis_diag(rec, reads_in_place=True):
     if rec.entry == "strided":
         return d, "none"
     return "none", {"in_place": "fused"}.get(d, d)
+
+
+def synthesis_launches(rec, chunk_blocks=0):
+    """(class-1, class-2) profiler records of the call: every chunk of a block range gives one
+    channel-IFFT and one block launch (synthesis_chunk), and a range of nb > 0 blocks is
+    ceil(nb / CB) chunks (synthesis_range; CB = chunk_blocks, or the whole range when 0: the default
+    chunk is far larger than any range of the tables here).  The split path runs the ranges
+    [0, b_s) and [b_s, B), every other path [0, B), each only when the call returns samples; a
+    rejected call launches nothing."""
+    if rec.path == "rejected" or rec.rows <= 0:
+        return 0, 0
+    ranges = [(0, rec.b_s), (rec.b_s, rec.blocks)] if rec.path.startswith("split") else [(0, rec.blocks)]
+    n = sum(-(-(hi - lo) // (chunk_blocks if chunk_blocks > 0 else hi - lo)) for lo, hi in ranges if hi > lo)
+    return n, n
 
 
 # ============================================================================ sequence tables

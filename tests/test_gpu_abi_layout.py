@@ -593,7 +593,7 @@ def _ifb_exec(lib, plan, fin, n_in, fout, cap, dev, mem=DEVICE):
 def test_inverse_filterbank_layout(gpu, N, nf, ov, chunks):
     """pfb_inverse_filterbank_execute over three chunks, framed against contiguous: the first
     call reads the input in place, the later ones carry rows and take the in-place carry
-    path (`Bc > 0 && !has_spectral && input_idat >= Bc`: ifb_exec, split path): the first blocks from a stitched
+    path (`Bc > 0 && !has_spectral && input_idat >= Bc`: ifb_go, split path): the first blocks from a stitched
     buffer of carry + input head, the rest from the input with a row shift.  There is no
     length query for this entry point: *n_out must equal the InverseFilterBank.m oracle's
     length, which is also the contiguous run's exact stride and capacity."""

@@ -1,4 +1,4 @@
-"""Stream objects at the boundaries of their carry paths (filterbank_exec and ifb_exec,
+"""Stream objects at the boundaries of their carry paths (filterbank_exec and ifb_go,
 ska-pst-dsp-model_amd/csrc/pfb_api_analysis.hip and pfb_api_synthesis.hip), through every entry point of the C ABI.
 
 tests/stream_model.py restates the two host state machines in integers and holds the call
@@ -14,7 +14,8 @@ the rejected call).  Here every sequence runs on the GPU:
   * after every call: same shape, bit-identical values (after undoing a strided layout), same
     buffered count, rows / output length and buffered count equal to the model, the
     last_dada_input / last_strided_input value include/pfb_api.h specifies, and for the analysis
-    one class-0 profiler record for a call that returns rows and none for one that does not;
+    one class-0 profiler record for a call that returns rows and none for one that does not, for the
+    synthesis the class-1 and class-2 records of the model's chunks (stream_model.synthesis_launches);
   * every chunk against the float64 oracle stream object at conftest.PARITY_TOL, and a Bunton
     stream against one pfb_analysis_execute of the whole series, bit for bit.
 
@@ -425,7 +426,7 @@ def _synth_call(gpu, plan, entry, xh, raw, out):
     return got
 
 
-def _drive_synthesis(gpu, kind, so, rot):
+def _drive_synthesis(gpu, launches, kind, so, rot, chunk_blocks=0):
     import torch
     pfb = _pfb()
     shape, rows, _, _, _, in_place = _synth_case(kind, so)
@@ -433,6 +434,9 @@ def _drive_synthesis(gpu, kind, so, rot):
     raw, x = _synth_samples(kind, so)
     oracle = _synth_oracle(kind, so)
     plan, twin = _synth_plan(kind, so), _synth_plan(kind, so)
+    if chunk_blocks:
+        plan.set_chunk_blocks(chunk_blocks)
+        twin.set_chunk_blocks(chunk_blocks)
     assert (plan.input_keep, plan.output_keep) == (shape.keep, shape.Lkeep)
     Bc, a, rejected, paths = 0, 0, 0, []
     for i, n in enumerate(rows):
@@ -448,9 +452,12 @@ def _drive_synthesis(gpu, kind, so, rot):
             rejected += 1
             assert oracle[i] is None, w
             out = torch.full((N_POL, 64), SENTINEL, dtype=torch.complex64, device=gpu)
+            launches.reset()
             with pytest.raises(pfb.PfbError) as e:
                 _synth_call(gpu, plan, entry, xh, rw, None if entry == "host" else out)
             assert e.value.status == pfb._lib.PFB_ERR_INVALID_ARG, w
+            torch.cuda.synchronize(gpu)
+            assert (launches.records(1), launches.records(2)) == sm.synthesis_launches(rec) == (0, 0), w
             with pytest.raises(pfb.PfbError):
                 twin.execute(xd, stateful=True, layout="ptc", out=out)
             torch.cuda.synchronize(gpu)
@@ -459,7 +466,10 @@ def _drive_synthesis(gpu, kind, so, rot):
             a += n
             continue
         assert plan.output_length(Bc + n) >= rec.rows, w
+        launches.reset()
         got = _synth_call(gpu, plan, entry, xh, rw, None)
+        torch.cuda.synchronize(gpu)
+        n_launch = (launches.records(1), launches.records(2))
         diag = (plan.last_strided_input(), plan.last_dada_input())
         ref = twin.execute(xd, stateful=True, layout="ptc").cpu().numpy()
         assert (twin.last_strided_input(), twin.last_dada_input()) == ("none", "none"), w
@@ -469,6 +479,7 @@ def _drive_synthesis(gpu, kind, so, rot):
         assert plan.buffered_samples == twin.buffered_samples == rec.carry_after, (
             w, plan.buffered_samples, twin.buffered_samples, rec.carry_after)
         assert diag == sm.synthesis_diag(rec, in_place), (w, diag, rec.path)
+        assert n_launch == sm.synthesis_launches(rec, chunk_blocks), (w, n_launch, rec.path)
         oref, obuf = oracle[i]
         assert obuf == rec.carry_after and oref.shape == (N_POL, 1, rec.rows), (w, obuf, oref.shape)
         if rec.rows:
@@ -482,20 +493,24 @@ def _drive_synthesis(gpu, kind, so, rot):
 
 @pytest.mark.parametrize("rot", range(len(SYNTH_ENTRIES)))
 @pytest.mark.parametrize("so", [0, 5])
-def test_inverse_filterbank_c2_stream_edges(gpu, so, rot):
+def test_inverse_filterbank_c2_stream_edges(gpu, launches, so, rot):
     """Sequence 5: 256 channels, Nf 256, Ov 48, tukey, deripple, two pols.  Offset 0: carry 160
     then 96 rows (input_idat == carry, every block stitched, the in-place range empty).  Offset
     5: 165 rows (the carry rounded up to a multiple of nu, the output shorter than the blocks',
     inside the split path).  Both: a zero-length call and a 3-row call every entry rejects.
     Entries: packed, host, pols interleaved in the row with a spare channel, channel-major,
     DADA NBIT 16 TFP, DADA LowCBF order (TFP for the chunks that are no multiple of 32)."""
-    _drive_synthesis(gpu, "c2", so, rot)
+    _drive_synthesis(gpu, launches, "c2", so, rot)
 
 
-@pytest.mark.parametrize("rot", range(len(SYNTH_ENTRIES)))
-@pytest.mark.parametrize("so", [0, 5])
-def test_inverse_filterbank_small_block_stream_edges(gpu, so, rot):
+@pytest.mark.parametrize(
+    "so, rot, chunk_blocks",
+    [pytest.param(so, rot, 0, id=f"{so}-{rot}") for so in (0, 5) for rot in range(len(SYNTH_ENTRIES))]
+    + [pytest.param(so, 0, 1, id=f"{so}-0-chunk1") for so in (0, 5)])
+def test_inverse_filterbank_small_block_stream_edges(gpu, launches, so, rot, chunk_blocks):
     """Sequence 6: 8 channels, Nf 128, Ov 16 (the small block kernel) with a Hann temporal
     taper: the strided and DADA entries are staged whole (their loaders have no per-channel
-    gain) inside the split path; the same recipe at keep = 96."""
-    _drive_synthesis(gpu, "small", so, rot)
+    gain) inside the split path; the same recipe at keep = 96.  chunk_blocks 1 (rotation 0, both
+    offsets): every block range runs one chunk per block, so the chunks after the first of a
+    range read their rows past a moved first row of the source."""
+    _drive_synthesis(gpu, launches, "small", so, rot, chunk_blocks)

@@ -1,4 +1,4 @@
-"""CPU checks of tests/stream_model.py, the integer restatement of filterbank_exec and ifb_exec
+"""CPU checks of tests/stream_model.py, the integer restatement of filterbank_exec and ifb_check / ifb_go
 (ska-pst-dsp-model_amd/csrc/pfb_api_analysis.hip, pfb_api_synthesis.hip):
 
   * it reproduces what the GPU suite already asserts of the real plans (the carries of
@@ -206,6 +206,29 @@ def test_c2_synthesis_tables_are_the_stated_ones():
     r5 = sm.synthesis_stream(sm.C2_SYNTH[5], sm.C2_SYNTH_ROWS[5])
     assert [r.carry_after for r in r5[:4]] == [224, 256, 160, 192]
     assert (r5[7].n_in, r5[7].path, r5[7].rows, r5[7].full) == (165, "split(2, 2)", 71008, 71680)
+
+
+@pytest.mark.parametrize("shapes, rows, entry, chunk_blocks, so, want", [
+    # split(b_s, B) is two ranges, [0, b_s) and [b_s, B); a call without samples launches nothing
+    (sm.C2_SYNTH, sm.C2_SYNTH_ROWS, "packed", 0, 0, [1, 1, 1, 2, 1, 1, 0, 1, 0, 2]),
+    (sm.C2_SYNTH, sm.C2_SYNTH_ROWS, "packed", 0, 5, [1, 0, 1, 2, 1, 0, 0, 1, 0, 2]),
+    (sm.C2_SYNTH, sm.C2_SYNTH_ROWS, "host", 0, 0, [1, 1, 1, 1, 1, 1, 0, 1, 0, 1]),
+    (sm.C2_SYNTH, sm.C2_SYNTH_ROWS, "host", 0, 5, [1, 0, 1, 1, 1, 0, 0, 1, 0, 1]),
+    (sm.SMALL_SYNTH, sm.SMALL_SYNTH_ROWS, "packed", 0, 0, [1, 0, 1, 2, 1, 0, 1, 0, 1, 0, 2]),
+    (sm.SMALL_SYNTH, sm.SMALL_SYNTH_ROWS, "packed", 0, 5, [1, 1, 1, 2, 1, 0, 1, 0, 1, 0, 2]),
+    (sm.SMALL_SYNTH, sm.SMALL_SYNTH_ROWS, "host", 0, 0, [1, 0, 1, 1, 1, 0, 1, 0, 1, 0, 1]),
+    (sm.SMALL_SYNTH, sm.SMALL_SYNTH_ROWS, "host", 0, 5, [1, 1, 1, 1, 1, 0, 1, 0, 1, 0, 1]),
+    # one chunk per block: the number of blocks, whatever the path
+    (sm.SMALL_SYNTH, sm.SMALL_SYNTH_ROWS, "packed", 1, 0, [2, 0, 1, 4, 1, 0, 1, 0, 1, 0, 6]),
+    (sm.SMALL_SYNTH, sm.SMALL_SYNTH_ROWS, "packed", 1, 5, [1, 1, 1, 4, 1, 0, 1, 0, 1, 0, 6]),
+    (sm.SMALL_SYNTH, sm.SMALL_SYNTH_ROWS, "host", 1, 0, [2, 0, 1, 4, 1, 0, 1, 0, 1, 0, 6]),
+    (sm.C2_SYNTH, sm.C2_SYNTH_ROWS, "packed", 4, 0, [1, 1, 1, 2, 1, 1, 0, 1, 0, 3]),
+])
+def test_synthesis_launch_counts_of_the_tables(shapes, rows, entry, chunk_blocks, so, want):
+    """synthesis_launches on the committed sequences: one channel-IFFT and one block launch per chunk."""
+    recs = sm.synthesis_stream(shapes[so], rows[so], entry)
+    assert [sm.synthesis_launches(r, chunk_blocks) for r in recs] == [(n, n) for n in want]
+    assert all(sm.synthesis_launches(r, chunk_blocks) == (0, 0) for r in recs if r.path == "rejected" or not r.rows)
 
 
 def test_rotations_cover_every_entry_at_every_call():
