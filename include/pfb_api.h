@@ -27,6 +27,26 @@
  *
  * Threading: a plan is bound to one device and is not thread safe (it carries the
  * streaming state).  Different plans are independent; multi-GPU = one plan per GPU.
+ *
+ * Streams (pinned by tests/test_gpu_streams.py; the fork and join of the pipelined round
+ * trip by tests/test_gpu_roundtrip.py):
+ *   - Every device operation of a call — kernels, copies, memsets, the moves of a stream
+ *     object's carry — is enqueued on the `stream` the call is given and on no other; the
+ *     call returns when they are enqueued (the PFB_MEM_HOST paths, pfb_quantize with a
+ *     `scale` and the pfb_purity_score_* functions also wait for that stream).  Nothing is
+ *     ordered against the default stream or any other stream of the process.
+ *   - The round trip (pfb_roundtrip_*) in its pipelined form runs its analysis on a
+ *     stream of the plan's own, which is forked from the given stream at the start of the
+ *     call and joined to it before the call returns; the fused form uses the given stream
+ *     alone.  Either way the call is, to the caller, work on the given stream.
+ *   - The plan-free utilities (pfb_dada_*, pfb_gather_channels, pfb_corner_turn,
+ *     pfb_quantize, pfb_testvec_generate, pfb_purity_score_*) share no device state across
+ *     streams: calls on different streams, from one host thread or several, may overlap
+ *     (one caveat for a captured pfb_quantize: see there).
+ *   - A plan may be called on different streams in turn, but its buffers (carry, scratch,
+ *     staging) are reused from call to call and nothing inside the plan orders one call
+ *     after the one before: the caller orders consecutive calls of one plan that go to
+ *     different streams (an event recorded after the first and waited on before the next).
  */
 #ifndef PFB_API_H
 #define PFB_API_H
@@ -665,7 +685,13 @@ pfb_status pfb_corner_turn(const pfb_cf32* in, int64_t in_outer_stride, int64_t 
  * "all")) over all n_pol x n samples, or 1 when rms <= 0 (Matlab round: half away from
  * zero).  Replaces FilterBank.m:75-83 (rndInput/rmsInput) and :106-113
  * (rndOutput/rmsOutput).  in == out is allowed.  Device memory; asynchronous unless
- * `scale` is non-null (then it receives the scale and the call synchronises). */
+ * `scale` is non-null (then it receives the scale and the call synchronises).  The moments
+ * are summed in a 32-byte block that belongs to the (device, stream) of the call: the first
+ * call on a stream allocates it (make that call before capturing the stream into a graph),
+ * none after it allocates, and calls on different streams share nothing.  A call captured
+ * into a graph keeps the block of the stream it was captured on wherever the graph is
+ * replayed: order such a graph's replays against the other calls made on that stream, as
+ * calls on one stream are ordered. */
 pfb_status pfb_quantize(const pfb_cf32* in, int64_t in_pol_stride, int64_t n, int32_t n_pol,
                         double rms, pfb_cf32* out, int64_t out_pol_stride, double* scale,
                         void* stream);

@@ -504,6 +504,17 @@ static pfb_status fb_rows_dst(pfb_analysis_plan* p, AnaLaunch& l, float2* out, i
   return PFB_OK;
 }
 
+// The size of either carry buffer for a carry of nb samples per pol: room for the longest carry
+// a stream call leaves, so that the buffer is allocated once.  nb = total - Kt M with
+// K - Kt < nu and total < P N + (K + 1) M (fb_lens, analysis_K; the padded and LowCBF counts
+// are smaller), so nb < P N + nu M.  Sized by nb alone the two buffers, which swap, regrew
+// from call to call, and a regrow frees the old block: hipFree waits for the whole device, so
+// a stream call stalled behind every stream of the process (tests/test_gpu_streams.py).
+static size_t fb_carry_bytes(const pfb_analysis_plan* p, int64_t nb) {
+  const int64_t most = (int64_t)p->P * p->N + (int64_t)p->nu * p->M;
+  return (size_t)p->n_pol * std::max(nb, most) * sizeof(float2);
+}
+
 // The call's tail: the next carry, nb samples per pol (packed cf32, whatever the input was),
 // into `into` — unpacked from the section `sec` at sample t0, else copied from src (pol stride
 // sps), else (neither) already written there by the launch — and the new count.  `into` is the
@@ -512,7 +523,7 @@ static pfb_status fb_rows_dst(pfb_analysis_plan* p, AnaLaunch& l, float2* out, i
 static pfb_status fb_carry(pfb_analysis_plan* p, pfb_analysis_plan::DevBuf& into, int64_t nb, const DadaSection* sec,
                            int64_t t0, const float2* src, int64_t sps, hipStream_t s) {
   if (nb > 0) {
-    HIPCHK(into.ensure((size_t)p->n_pol * nb * sizeof(float2)));
+    HIPCHK(into.ensure(fb_carry_bytes(p, nb)));
     if (sec) {
       const pfb_status st = section_unpack(p, *sec, t0, nb, into.as<float2>(), nb, s);
       if (st != PFB_OK) return st;
@@ -599,7 +610,7 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
       // no copy launch after it — and the two buffers swap
       CarryOut co{nullptr, input_idat - B, nb, nb};
       if (nb > 0) {
-        HIPCHK(p->carry_next.ensure((size_t)p->n_pol * nb * sizeof(float2)));
+        HIPCHK(p->carry_next.ensure(fb_carry_bytes(p, nb)));
         co.dst = p->carry_next.as<float2>();
       }
       l.in = (const float2*)in;

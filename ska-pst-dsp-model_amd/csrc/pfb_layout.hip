@@ -23,7 +23,10 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <map>
 #include <mutex>
+#include <thread>
+#include <tuple>
 #include <vector>
 
 #include "pfb_api.h"
@@ -361,24 +364,37 @@ __global__ void __launch_bounds__(TPB) quantize_kernel(const float2* __restrict_
   }
 }
 
-// per-device scratch for the moments (4 doubles), allocated once per device
+// Scratch for the moments (4 doubles): one block per (device, stream), allocated at the first
+// call on that stream and never freed.  A call's memset, atomics and reads of its block are
+// ordered by its stream, so calls on different streams share nothing; a stream handle that
+// the runtime reuses after hipStreamDestroy finds the old block, which is harmless for the
+// same reason.  hipStreamPerThread is one handle for a different stream in every host
+// thread, so its blocks are keyed by the thread as well.  The map only grows: a process that
+// creates and destroys streams without end leaves 32 bytes of device memory and a map node per
+// handle value it ever quantised on (the runtime reuses handle values, which bounds it in
+// practice).  A captured call keeps its capture stream's block at every replay (pfb_api.h).
 struct Scratch {
   std::mutex mu;
-  std::vector<double*> per_dev;
+  std::map<std::tuple<int, hipStream_t, std::thread::id>, double*> blocks;
 };
 Scratch g_scratch;
 
-hipError_t stats_buffer(double** out) {
+hipError_t stats_buffer(hipStream_t s, double** out) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
+  const auto key = std::make_tuple(dev, s, s == hipStreamPerThread ? std::this_thread::get_id()
+                                                                    : std::thread::id());
   std::lock_guard<std::mutex> lk(g_scratch.mu);
-  if ((int)g_scratch.per_dev.size() <= dev) g_scratch.per_dev.resize(dev + 1, nullptr);
-  if (!g_scratch.per_dev[dev]) {
-    e = hipMalloc(&g_scratch.per_dev[dev], 4 * sizeof(double));
-    if (e != hipSuccess) return e;
+  double*& block = g_scratch.blocks[key];
+  if (!block) {
+    e = hipMalloc(&block, 4 * sizeof(double));
+    if (e != hipSuccess) {
+      block = nullptr;
+      return e;
+    }
   }
-  *out = g_scratch.per_dev[dev];
+  *out = block;
   return hipSuccess;
 }
 
@@ -505,7 +521,7 @@ pfb_status pfb_quantize(const pfb_cf32* in, int64_t in_pol_stride, int64_t n, in
   if (rms > 0 && n * (int64_t)n_pol < 2) return bad("pfb_quantize: var() of a single sample");
   hipStream_t s = (hipStream_t)stream;
   double* st = nullptr;
-  HIPCHK(stats_buffer(&st));
+  HIPCHK(stats_buffer(s, &st));
   if (n_pol > 65535) return bad("pfb_quantize: n_pol > 65535");
   const dim3 g(std::max(1u, grid_stride_blocks(n * n_pol) / (unsigned)n_pol), (unsigned)n_pol);
   if (rms > 0) {
