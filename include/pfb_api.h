@@ -190,13 +190,18 @@ int64_t pfb_filterbank_output_rows(const pfb_analysis_plan* plan, int64_t n_in);
  * 4096-point row FFT stores channel-major output as 16-byte row pairs when `out` is 16-byte
  * aligned and out_pol_stride and chan_stride are even, else as 8-byte elements.  (The
  * Bunton streaming kernel range-limits each 16-row step with a buffer descriptor, whose
- * extent 64 row_stride + j_max chan_stride must fit 2^31 bytes, else PFB_ERR_UNSUPPORTED.)
+ * extent must fit 32-bit offsets: (64 row_stride + jn chan_stride + 1) * 8 <= 0x7ffffff0 with
+ * jn = sel_n, or n_chan without a chomp, else PFB_ERR_UNSUPPORTED — row_stride 1 admits
+ * chan_stride <= 1048575 at 256 bins, chan_stride 1 admits row_stride <= 4194299.)
  * Checks, all before any launch or change of the stream state: a bad layout (a stride
  * <= 0, a negative sel_*, sel_split + sel_shift or sel_n beyond the channels) or
  * in_pol_stride < n_in is PFB_ERR_INVALID_ARG; out_capacity is the number of pfb_cf32
  * elements available from `out`: a call whose furthest written element ((n_pol-1)
  * out_pol_stride + (rows-1) row_stride + (j_max) chan_stride) lies beyond it fails with
- * PFB_ERR_BUFFER_TOO_SMALL and writes nothing. */
+ * PFB_ERR_BUFFER_TOO_SMALL and writes nothing.  *n_out: the layout checks (the plan, the
+ * strides and sel_*, the stride and extent limits above) come first, and a call they refuse
+ * (PFB_ERR_INVALID_ARG, PFB_ERR_UNSUPPORTED) leaves *n_out as it was; every later outcome,
+ * PFB_ERR_BUFFER_TOO_SMALL included, has set it to T_out. */
 pfb_status pfb_filterbank_execute_strided(pfb_analysis_plan* plan, const pfb_cf32* in,
                                           int64_t in_pol_stride, int64_t n_in, pfb_cf32* out,
                                           int64_t out_pol_stride, int64_t row_stride,
@@ -410,7 +415,10 @@ int32_t pfb_synthesis_last_dada_input(const pfb_synthesis_plan* plan);
  * tap phases, and PFB_ANALYSIS_LOWCBF; stateless and stream calls — a stream call reads the
  * carry through its cf32 descriptor in the same launch) or on the LDS-shared FIR of the
  * n_chan > 256 path (os 8/7 or 4/3, <= 32 phases; the stateless call, and a stream call with
- * nothing buffered).  No byte outside the section is loaded, and of a two-polarisation section
+ * nothing buffered).  Descriptor limit: 512 rows of one workgroup at n_pol * 2 * nbit / 8 bytes
+ * per sample must fit 32-bit offsets, n_pol * (nbit / 4) * n_chan * 512 <= 0x7ffffff0 (n_chan
+ * 256: n_pol <= 2047 / 4095 / 8191 at NBIT 32 / 16 / 8); more polarisations are STAGED.  No
+ * byte outside the section is loaded, and of a two-polarisation section
  * a workgroup loads only its own polarisation's samples.  STAGED: every other format (NBIT
  * 64, NDIM 1, LowCBF order, a misaligned section), plan or stream state is unpacked into a
  * plan-owned buffer — a stream call's samples straight behind the carry in the concatenation
@@ -453,7 +461,9 @@ int32_t pfb_analysis_last_dada_input(const pfb_analysis_plan* plan);
  * store of 2 / 4 / 8 bytes per complex sample, and the cf32 product never crosses HBM —
  * out_nbit 8, 16 or 32, `out` aligned to one complex sample, and a plan on the streaming
  * kernel (PFB_ANALYSIS_BUNTON with n_chan 256, os 8/7 or 4/3, 12 or 13 tap phases, and
- * PFB_ANALYSIS_LOWCBF; stateless and stream calls).  The _dada_to_dada calls read the input
+ * PFB_ANALYSIS_LOWCBF; stateless and stream calls).  Descriptor limit: the 16 rows of one step
+ * must fit 32-bit offsets, 16 * C * P * (out_nbit / 4) <= 0x7ffffff0 (C and P as above), which
+ * holds for every plan (P <= 65535).  The _dada_to_dada calls read the input
  * section in place as well when it qualifies for pfb_analysis_execute_dada's FUSED and its
  * nbit equals out_nbit or out_nbit is 32 (an integer file channelised into a float one); any
  * other input section is unpacked into the plan's staging buffer first and the output stays
@@ -510,7 +520,10 @@ int32_t pfb_analysis_last_dada_output(const pfb_analysis_plan* plan);
  * buffer store of 2 / 4 / 8 bytes per complex sample, and the cf32 series never crosses HBM —
  * out_nbit 8, 16 or 32, `out` aligned to one complex sample, and a plan on that kernel
  * (input_fft_length 256, input_overlap 48, os 8/7 or 4/3, n_chan a multiple of 16, no spectral
- * taper).  The input side is the channel IFFT's own launch, so the _dada_to_dada calls read
+ * taper).  Descriptor limit: one block's L = 256 * de / nu * n_chan output samples must fit
+ * 32-bit offsets, L * n_pol * (out_nbit / 4) <= 0x7ffffff0 (n_chan 256, 8/7: n_pol <= 4681 at
+ * NBIT 32, 18724 at NBIT 8); more polarisations are STAGED.  The input side is the channel
+ * IFFT's own launch, so the _dada_to_dada calls read
  * their section as pfb_synthesis_execute_dada does (pfb_synthesis_last_dada_input reports it)
  * whatever the output takes.
  * STAGED: every other plan (input_fft_length 512, the block-kernel shapes, spectral tapers),
@@ -583,7 +596,9 @@ int32_t pfb_synthesis_last_dada_output(const pfb_synthesis_plan* plan);
  * runs (PFB_ANALYSIS_BUNTON, n_chan 256, os 8/7 or 4/3, 12 or 13 tap phases; input_fft_length
  * 256, input_overlap 48; no combine permutation, temporal-taper gain or spectral taper; no
  * chunk size set; (sample_offset - 1) a multiple of 16); sections within the descriptor limits
- * of pfb_analysis_execute_dada and pfb_analysis_execute_to_dada.  A half needs its own side's
+ * of pfb_analysis_execute_dada (P * (nbit / 4) * N * 512 <= 0x7ffffff0, N and P as above) and
+ * pfb_analysis_execute_to_dada (16 * C * P * (out_nbit / 4) <= 0x7ffffff0, here with C = N and
+ * out_nbit = 32, the float `chan` section).  A half needs its own side's
  * conditions only.  The stage-1 rows are STORED in these calls whatever
  * pfb_synthesis_set_stage1_rows says (no recomputing kernel reads a section);
  * pfb_synthesis_last_stage1_rows reports it.
