@@ -32,8 +32,9 @@
  * trip by tests/test_gpu_roundtrip.py):
  *   - Every device operation of a call — kernels, copies, memsets, the moves of a stream
  *     object's carry — is enqueued on the `stream` the call is given and on no other; the
- *     call returns when they are enqueued (the PFB_MEM_HOST paths, pfb_quantize with a
- *     `scale` and the pfb_purity_score_* functions also wait for that stream).  Nothing is
+ *     call returns when they are enqueued (the PFB_MEM_HOST paths, pfb_quantize and the
+ *     *_quantised_to_dada calls with a `scale`, and the pfb_purity_score_* functions also
+ *     wait for that stream).  Nothing is
  *     ordered against the default stream or any other stream of the process.
  *   - The round trip (pfb_roundtrip_*) in its pipelined form runs its analysis on a
  *     stream of the plan's own, which is forked from the given stream at the start of the
@@ -44,7 +45,7 @@
  *     streams: calls on different streams, from one host thread or several, may overlap
  *     (one caveat for a captured pfb_quantize: see there).
  *   - A plan may be called on different streams in turn, but its buffers (carry, scratch,
- *     staging) are reused from call to call and nothing inside the plan orders one call
+ *     staging, the quantised calls' product, partial sums and stats block) are reused from call to call and nothing inside the plan orders one call
  *     after the one before: the caller orders consecutive calls of one plan that go to
  *     different streams (an event recorded after the first and waited on before the next).
  */
@@ -497,6 +498,85 @@ pfb_status pfb_filterbank_execute_dada_to_dada(pfb_analysis_plan* plan, const vo
                                                int32_t out_nbit, float out_scale,
                                                int64_t out_capacity_bytes, int64_t* n_out, void* stream);
 int32_t pfb_analysis_last_dada_output(const pfb_analysis_plan* plan);
+
+/* The FilterBank's quantised output as a DADA data section (FilterBank.m:106-113 followed by
+ * write_dada_data.m:32-50): the product is rescaled to the target rms, rounded to integers,
+ * multiplied by out_scale and stored at out_nbit.  With x the cf32 product of the
+ * corresponding *_to_dada call (rows [0, *n_out) of every polarisation, cnt = rows * C * P
+ * complex samples):
+ *   scale = rms / sqrt(var),  var = (sum |x|^2 - ((sum re)^2 + (sum im)^2) / cnt) / (cnt - 1)
+ * (var(x, 0, "all"), summed in double; a zero variance is not special-cased, as in
+ * pfb_quantize), and per component
+ *   q = roundf((float)scale * x),  y = out_scale * q (float32),  sample = cast(y)
+ * with pfb_dada_pack's cast (round half away from zero, saturate): the operations of
+ * pfb_quantize, a float32 scale pass and pfb_dada_pack, in that order — given the same float32
+ * scale, their bytes.  rms <= 0: round only ((float)scale = 1, no moments are taken).
+ * The section layout, *n_out, the status codes, pfb_filterbank_buffered,
+ * pfb_filterbank_output_rows, the carry and the LowCBF first-call pre-padding are those of the
+ * matching *_to_dada call; exactly rows [0, *n_out) are written and not one byte beyond.  Every
+ * check runs before any launch or state change: a rejected call leaves `out`, the carry and the
+ * pending pre-padding untouched.  PFB_ERR_INVALID_ARG: the *_to_dada conditions and a
+ * non-finite rms.  PFB_ERR_BUFFER_TOO_SMALL, with nothing written: out_capacity_bytes below
+ * rows * C * P * 2 * out_nbit / 8.  A call that yields 0 rows writes nothing, sets *scale = 1
+ * and advances the stream state as the cf32 call does.
+ * FUSED: a plan on the streaming kernel (as for *_to_dada's FUSED, any out_nbit).  Three
+ * launches: the analysis kernel, which stores the cf32 product into a buffer of the plan and
+ * sums the moments of exactly the values it stores (per-workgroup partial sums, ordinary
+ * stores); one workgroup that adds the partial sums in a fixed order and forms the scale; one
+ * pass that reads the product once and writes the section.
+ * STAGED: every other plan (padded, the one-launch N <= 256 kernel, FIR + row FFT), or
+ * pfb_analysis_set_quantiser_moments(plan, PFB_QUANTISER_MOMENTS_STAGED): the plan's cf32 path
+ * into the same buffer, one pass over it for the partial sums, then the same two launches.
+ * PFB_QUANTISER_MOMENTS_FUSED on a plan that cannot take it: PFB_ERR_UNSUPPORTED from the
+ * execute call, nothing launched.  AUTO (the default) takes FUSED where the plan allows it.
+ * The _dada calls read the input section in place wherever pfb_analysis_execute_dada does,
+ * whatever out_nbit is; any other section is unpacked into the plan's staging buffer first.
+ * pfb_analysis_last_quantiser: the path of the plan's last such call (of the product, also
+ * when rms <= 0), NONE before one or after a cf32-output or *_to_dada call, -1 for a null plan;
+ * pfb_analysis_last_dada_output then reports NONE.
+ * Streams: everything is enqueued on the given stream.  The product buffer, the partial sums
+ * and the 32-byte block {sum re, sum im, sum |x|^2, scale} belong to the plan — nothing is
+ * shared per device or per stream — and grow only with the call's length, like the plan's
+ * other call-length buffers: the first call, or a longer one, may allocate and wait for the
+ * device.  With scale == NULL the call does not wait for the device and can be captured into a
+ * graph (after one call of that length outside the capture); with scale non-null it copies
+ * the double back and synchronises the stream.
+ * Determinism: no floating-point atomics; the same plan, input and launch grid give the same
+ * scale bits and the same bytes.  (Measured A/B against the pair: DESIGN.md §4.11.) */
+typedef enum pfb_quantiser_moments {
+  PFB_QUANTISER_MOMENTS_AUTO = 0,
+  PFB_QUANTISER_MOMENTS_FUSED = 1,
+  PFB_QUANTISER_MOMENTS_STAGED = 2
+} pfb_quantiser_moments;
+typedef enum pfb_quantiser {
+  PFB_QUANTISER_NONE = 0,
+  PFB_QUANTISER_FUSED = 1,
+  PFB_QUANTISER_STAGED = 2
+} pfb_quantiser;
+pfb_status pfb_analysis_execute_quantised_to_dada(pfb_analysis_plan* plan, const pfb_cf32* in,
+                                                  int64_t in_pol_stride, int64_t n_dat, double rms,
+                                                  void* out, int32_t out_nbit, float out_scale,
+                                                  int64_t out_capacity_bytes, int64_t* n_out,
+                                                  double* scale, void* stream);
+pfb_status pfb_filterbank_execute_quantised_to_dada(pfb_analysis_plan* plan, const pfb_cf32* in,
+                                                    int64_t in_pol_stride, int64_t n_in, double rms,
+                                                    void* out, int32_t out_nbit, float out_scale,
+                                                    int64_t out_capacity_bytes, int64_t* n_out,
+                                                    double* scale, void* stream);
+pfb_status pfb_analysis_execute_dada_quantised_to_dada(pfb_analysis_plan* plan, const void* in,
+                                                       int32_t nbit, int32_t ndim, int32_t order,
+                                                       int64_t n_dat, double rms, void* out,
+                                                       int32_t out_nbit, float out_scale,
+                                                       int64_t out_capacity_bytes, int64_t* n_out,
+                                                       double* scale, void* stream);
+pfb_status pfb_filterbank_execute_dada_quantised_to_dada(pfb_analysis_plan* plan, const void* in,
+                                                         int32_t nbit, int32_t ndim, int32_t order,
+                                                         int64_t n_in, double rms, void* out,
+                                                         int32_t out_nbit, float out_scale,
+                                                         int64_t out_capacity_bytes, int64_t* n_out,
+                                                         double* scale, void* stream);
+pfb_status pfb_analysis_set_quantiser_moments(pfb_analysis_plan* plan, int32_t mode);
+int32_t pfb_analysis_last_quantiser(const pfb_analysis_plan* plan);
 
 /* Synthesis writing its output straight into a DADA data section (polyphase_synthesis /
  * InverseFilterBank.m:92-96 followed by write_dada_data.m:32-50): the single-channel TFP

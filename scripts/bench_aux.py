@@ -21,6 +21,10 @@ one MI355X, as algorithmic HBM bytes / time against the 8 TB/s peak.
     channelised and the output sections at the C2 unit, the sequence (pfb_dada_unpack,
     pfb_roundtrip_execute, packs) against pfb_roundtrip_execute_dada_to_dada, interleaved, and
     the two halves pipelined over two streams
+  * --only-quantised-output: the FilterBank's rms-scaled, rounded output as a DADA section at the
+    C2 shape, what the object enqueues today (execute, pfb_quantize, the copy, pfb_dada_pack)
+    against pfb_analysis_execute_quantised_to_dada in AUTO and in STAGED mode and the plain
+    pfb_analysis_execute_to_dada as the floor, interleaved
   * --only-twostage-inverse: TwoStageInverseFilterBank with the channel gather against the
     strided input (pfb_inverse_filterbank_execute_strided), interleaved
 
@@ -74,6 +78,9 @@ def main():
                     help="the dada_synthesis_output A/B alone (--reps: calls per timed window)")
     ap.add_argument("--only-dada-roundtrip", action="store_true",
                     help="the dada_roundtrip A/B alone (--reps: calls per timed window)")
+    ap.add_argument("--only-quantised-output", action="store_true",
+                    help="the quantised_output A/B alone (--reps: calls per timed window, at least 20; "
+                         "--rounds: windows, at least 9)")
     ap.add_argument("--only-twostage-inverse", action="store_true",
                     help="the inverse cascade's gather vs strided-input A/B alone (--reps: calls per window)")
     ap.add_argument("--rounds", type=int, default=15,
@@ -118,6 +125,8 @@ def main():
         return dada_synthesis_output(torch, pfb, dev, max(args.reps, 20), args.rounds)
     if args.only_dada_roundtrip:
         return dada_roundtrip(torch, pfb, dev, max(args.reps, 20), args.rounds)
+    if args.only_quantised_output:
+        return quantised_output(torch, pfb, dev, max(args.reps, 20), max(args.rounds, 9))
     if args.only_twostage_inverse:
         return twostage_inverse(torch, pfb, noise, max(args.reps, 20), max(args.rounds, 5))
     # ---- C2' (4/3) round trip
@@ -474,6 +483,153 @@ def dada_output(torch, pfb, dev, reps, rounds):
             flush=True)
         del plan, src, cf, scaled, sec_a, sec_b
         torch.cuda.empty_cache()
+
+
+def quantised_output(torch, pfb, dev, reps, rounds, sides=("A", "A_nocopy", "B", "Bs", "floor")):
+    """The FilterBank's output quantiser (FilterBank.m:106-113) into a DADA section at the C2 shape
+    (256 ch, 8/7, 2^24 samples), through the C ABI into preallocated buffers.
+    A: what FilterBank enqueues today — the cf32 execute (pfb_analysis_execute, or _dada for an
+    NBIT 16 section), pfb_quantize(rms), the contiguous copy, pfb_dada_pack.  A_nocopy: the same
+    without the copy (FilterBank's view of a device product is already contiguous when it is
+    transposed back).  B: pfb_analysis_execute_quantised_to_dada in AUTO mode.  Bs: the same with
+    the moments STAGED.  floor: the plain pfb_analysis_execute_to_dada (no quantiser).
+    All sides are warmed, then `rounds` windows of `reps` calls of each side, alternating in one
+    process.  One line per case with the median, min, max and max - min of each side, whether the
+    sections are equal and whether A's and B's float32 scales have the same bits, and the
+    project's rule: the lower median wins when the difference exceeds the larger spread."""
+    from ctypes import byref, c_double, c_int64, c_void_p
+    from ska_pst_dsp_model_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator(device=dev).manual_seed(9)
+    taps = pfb.design_PFB_FIR_filter(256, "8/7", 12)
+    n, N = 1 << 24, 256
+    dts = {8: torch.int8, 16: torch.int16}
+    for in_nbit in (0, 16):
+        for n_pol in (1, 2):
+            for nbit in (8, 16):
+                plan = pfb.AnalysisPlan(taps, N, "8/7", "polyphase_analysis", n_pol)
+                K, C = plan.output_length(n), plan.out_chan
+                if in_nbit:
+                    src = torch.randint(-3000, 3000, (n * n_pol * 2,), dtype=torch.int16, device=dev, generator=g)
+                else:
+                    src = torch.view_as_complex(torch.randn((n_pol, n, 2), device=dev, generator=g) + 0.25)
+                cf = torch.empty((n_pol, K, C), dtype=torch.complex64, device=dev)
+                quant = torch.empty_like(cf)
+                copy = torch.empty_like(cf)
+                sec = {k: torch.empty((K, C, n_pol, 2), dtype=dts[nbit], device=dev) for k in sides}
+                nbytes = K * C * n_pol * 2 * (nbit // 8)
+                stream = c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                n_out = c_int64(0)
+                rms = 20.0 if nbit == 8 else 3000.0
+
+                def execute_cf32():
+                    if in_nbit:
+                        _lib.check(lib.pfb_analysis_execute_dada(plan._h, c_void_p(src.data_ptr()), in_nbit, 2,
+                                                                 _lib.PFB_DADA_TFP, n, c_void_p(cf.data_ptr()), K * C,
+                                                                 K, byref(n_out), stream))
+                    else:
+                        _lib.check(lib.pfb_analysis_execute(plan._h, c_void_p(src.data_ptr()), n, n,
+                                                            c_void_p(cf.data_ptr()), K * C, K, byref(n_out),
+                                                            _lib.PFB_MEM_DEVICE, stream))
+
+                def side_a(with_copy, scale=None):
+                    execute_cf32()
+                    _lib.check(lib.pfb_quantize(c_void_p(cf.data_ptr()), K * C, K * C, n_pol, rms,
+                                                c_void_p(quant.data_ptr()), K * C, scale, stream))
+                    packed = quant
+                    if with_copy:
+                        copy.copy_(quant)
+                        packed = copy
+                    _lib.check(lib.pfb_dada_pack(c_void_p(packed.data_ptr()), K * C, K, C, n_pol,
+                                                 c_void_p(sec["A" if with_copy else "A_nocopy"].data_ptr()), nbit,
+                                                 stream))
+
+                def side_b(key, scale=None):
+                    dst = c_void_p(sec[key].data_ptr())
+                    if in_nbit:
+                        _lib.check(lib.pfb_analysis_execute_dada_quantised_to_dada(
+                            plan._h, c_void_p(src.data_ptr()), in_nbit, 2, _lib.PFB_DADA_TFP, n, rms, dst, nbit, 1.0,
+                            nbytes, byref(n_out), scale, stream))
+                    else:
+                        _lib.check(lib.pfb_analysis_execute_quantised_to_dada(
+                            plan._h, c_void_p(src.data_ptr()), n, n, rms, dst, nbit, 1.0, nbytes, byref(n_out), scale,
+                            stream))
+
+                def side_bs(scale=None):
+                    _lib.check(lib.pfb_analysis_set_quantiser_moments(plan._h, _lib.PFB_QUANTISER_MOMENTS_STAGED))
+                    side_b("Bs", scale)
+                    _lib.check(lib.pfb_analysis_set_quantiser_moments(plan._h, _lib.PFB_QUANTISER_MOMENTS_AUTO))
+
+                def side_floor():
+                    dst = c_void_p(sec["floor"].data_ptr())
+                    if in_nbit:
+                        _lib.check(lib.pfb_analysis_execute_dada_to_dada(
+                            plan._h, c_void_p(src.data_ptr()), in_nbit, 2, _lib.PFB_DADA_TFP, n, dst, nbit, 1e-3,
+                            nbytes, byref(n_out), stream))
+                    else:
+                        _lib.check(lib.pfb_analysis_execute_to_dada(plan._h, c_void_p(src.data_ptr()), n, n, dst, nbit,
+                                                                    1e-3, nbytes, byref(n_out), stream))
+
+                fns = {"A": lambda: side_a(True), "A_nocopy": lambda: side_a(False), "B": lambda: side_b("B"),
+                       "Bs": side_bs, "floor": side_floor}
+                fns = {k: fns[k] for k in sides}
+                rec = {"kernel": "quantised_output", "shape": "C2 256ch 8/7", "samples": n, "n_pol": n_pol,
+                       "in": f"nbit{in_nbit}" if in_nbit else "cf32", "nbit": nbit, "rms": rms,
+                       "calls_per_window": reps, "windows": rounds}
+                # the scales and the sections, once
+                sa, sb, sbs = c_double(0), c_double(0), c_double(0)
+                if "A" in sides:
+                    side_a(True, byref(sa))
+                    rec["A_scale"] = sa.value
+                if "B" in sides:
+                    side_b("B", byref(sb))
+                    rec["B_scale"], rec["B_path"] = sb.value, plan.last_quantiser()
+                    rec["input_path"] = plan.last_dada_input()
+                if "Bs" in sides:
+                    side_bs(byref(sbs))
+                    rec["Bs_scale"], rec["Bs_path"] = sbs.value, plan.last_quantiser()
+                for k in sides:
+                    fns[k]()
+                torch.cuda.synchronize()
+                if "A" in sides and "B" in sides:
+                    rec["A_B_float32_scale_bits_equal"] = bool(np.float32(sa.value).tobytes() ==
+                                                               np.float32(sb.value).tobytes())
+                    rec["A_B_outputs_equal"] = bool(torch.equal(sec["A"], sec["B"]))
+                    rec["A_B_samples_differing"] = int((sec["A"] != sec["B"]).sum())
+                if "B" in sides and "Bs" in sides:
+                    rec["B_Bs_float32_scale_bits_equal"] = bool(np.float32(sb.value).tobytes() ==
+                                                                np.float32(sbs.value).tobytes())
+                    rec["B_Bs_outputs_equal"] = bool(torch.equal(sec["B"], sec["Bs"]))
+                if "A" in sides and "A_nocopy" in sides:
+                    rec["A_A_nocopy_outputs_equal"] = bool(torch.equal(sec["A"], sec["A_nocopy"]))
+                for _ in range(2):
+                    for k in sides:
+                        timeit(torch, fns[k], reps)
+                t = {k: [] for k in sides}
+                for _ in range(rounds):
+                    for k in sides:
+                        t[k].append(timeit(torch, fns[k], reps))
+                for k in sides:
+                    rec[f"{k}_ms"] = {"median": round(float(np.median(t[k])), 4), "min": round(float(min(t[k])), 4),
+                                      "max": round(float(max(t[k])), 4),
+                                      "spread": round(float(max(t[k]) - min(t[k])), 4)}
+
+                def wins(x, y):  # x's median below y's by more than the larger spread
+                    return bool(rec[f"{y}_ms"]["median"] - rec[f"{x}_ms"]["median"] >
+                                max(rec[f"{x}_ms"]["spread"], rec[f"{y}_ms"]["spread"]))
+                for x, y in (("B", "A"), ("B", "A_nocopy"), ("B", "Bs"), ("Bs", "B"), ("Bs", "A")):
+                    if x in sides and y in sides:
+                        rec[f"{x}_below_{y}_by_more_than_spread"] = wins(x, y)
+                esz_in, esz, prod = (2 * in_nbit // 8 if in_nbit else 8), 2 * nbit // 8, K * C * 8
+                # per polarisation: the input read; the product written and read back
+                rec["A_bytes"] = int(n_pol * (n * esz_in + prod + prod + 2 * prod + 2 * prod + prod + K * C * esz))
+                rec["A_nocopy_bytes"] = int(n_pol * (n * esz_in + prod + prod + 2 * prod + prod + K * C * esz))
+                rec["B_bytes"] = int(n_pol * (n * esz_in + 2 * prod + K * C * esz))
+                rec["Bs_bytes"] = int(n_pol * (n * esz_in + 3 * prod + K * C * esz))
+                rec["floor_bytes"] = int(n_pol * (n * esz_in + K * C * esz))
+                print(json.dumps(rec), flush=True)
+                del plan, src, cf, quant, copy, sec
+                torch.cuda.empty_cache()
 
 
 def dada_synthesis_output(torch, pfb, dev, reps, rounds):

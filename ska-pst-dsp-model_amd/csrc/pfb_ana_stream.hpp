@@ -129,6 +129,29 @@ struct DadaRowStore {
   }
 };
 
+// The quantised product's moments (analysis_stream_moments_kernel): a row store (BufRowStore /
+// LcbfRowStore) that forwards store() and adds the float32 value that goes to memory — after the
+// store's scale * v — into the thread's double sums m = {sum re, sum im, sum re^2 + im^2}.  A
+// sample counts only where the store lands: rows [lo, hi) of the step, and for LowCBF the 216
+// kept bins; a select, no branch and no memory operation.
+template <class ST, bool LCBF>
+struct MomentRowStore {
+  static constexpr bool kIsLds = false;
+  ST st;
+  int hi;
+  double* m;
+  __device__ __forceinline__ void store(int row, int f, float2 v) const {
+    st.store(row, f, v);
+    bool ok = (row >= st.lo) & (row < hi);
+    if constexpr (LCBF) ok = ok & (((f + 108) & 255) < 216);
+    const float2 x = cscale(v, st.scale);
+    const double re = ok ? (double)x.x : 0.0, im = ok ? (double)x.y : 0.0;
+    m[0] += re;
+    m[1] += im;
+    m[2] = fma(re, re, fma(im, im, m[2]));
+  }
+};
+
 // ZOUT (round trip): each step's channelised rows are also inverse-transformed across
 // channels in LDS and written as synthesis stage-1 rows (AnalysisArgs::z), so the
 // synthesis does not re-read them from HBM.
@@ -173,9 +196,12 @@ struct SinkStore {
 // OUT: the product's store (OutCf32, or a DADA section written in place: ZOUT 0, GS 0 — and the
 // file-to-file round trip's one combination, a section read in place, the NBIT 32 float product
 // section and the 2-row runs: ZOUT 2, IN a DADA class, OutDada32)
+// MOM: the plain cf32 product with its moments (MomentRowStore): the workgroup's three sums go
+// to a.mom[(pol nw + w) 3 ...] with ordinary stores, zeros from a workgroup without steps
 template <int N, int P, int NU, int DE, int ZOUT, bool LCBF, int GS, int TV = 0, class IN = InCf32,
-          class OUT = OutCf32>
+          class OUT = OutCf32, bool MOM = false>
 __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int pol, int w, int nw) {
+  static_assert(!MOM || (!OUT::kDada && ZOUT == 0 && GS == 0 && TV == 0), "moments: the plain cf32 product");
   static_assert(!OUT::kDada || (GS == 0 && TV == 0 &&
                                 (ZOUT == 0 || (ZOUT == 2 && !LCBF && IN::kDada && std::is_same<OUT, OutDada32>::value))),
                 "the DADA store: the plain product, or the round trip's float section with 2-row runs");
@@ -215,7 +241,14 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
   const int64_t q_lo = a.row0 / NU;
   const int64_t n_steps = ((a.K + NU - 1) / NU - q_lo + QS - 1) / QS;
   const int64_t st0 = n_steps * w / nw, st1 = n_steps * (w + 1) / nw;
+  if constexpr (MOM) {
+    if (st0 >= st1 && c == 0) {
+      double* slot = a.mom + ((int64_t)pol * nw + w) * 3;
+      slot[0] = slot[1] = slot[2] = 0.0;
+    }
+  }
   if (st0 >= st1) return;
+  [[maybe_unused]] double mom[3] = {0.0, 0.0, 0.0};
 
   // input column c from row DE q_first on; range-checked buffer loads return 0 past n_dat
   const int64_t row_first = (int64_t)DE * (q_lo + st0 * QS);
@@ -365,6 +398,10 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
       block_fft<N, -1, T, NT, kWR>(rows, st, rows, tw, c);
     } else if constexpr (LCBF) {
       const LcbfRowStore st = LcbfRowStore::rows(opol, k0, T, a.row0, a.K, a.lcbf_scale);
+      if constexpr (MOM) {
+        const int hi = (int)min(max(a.K - k0, (int64_t)0), (int64_t)T);
+        block_fft<N, -1, T, NT, kWR>(rows, MomentRowStore<LcbfRowStore, true>{st, hi, mom}, rows, tw, c);
+      } else
       block_fft<N, -1, T, NT, kWR>(rows, st, rows, tw, c);
     } else if constexpr (GS == 2) {
       // channel-major (a cascade's stage-2 series, out_rs = 1, no chomp): the last pass
@@ -402,6 +439,10 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
     } else {
       // (timing mask bit 1, experiments build: no channelised stores)
       const BufRowStore st = BufRowStore::rows(opol, k0, T, a.row0, (tmask(a.timing_mask) & 2) ? k0 : a.K, N, (float)N);
+      if constexpr (MOM) {
+        const int hi = (int)min(max(a.K - k0, (int64_t)0), (int64_t)T);
+        block_fft<N, -1, T, NT, kWR>(rows, MomentRowStore<BufRowStore, false>{st, hi, mom}, rows, tw, c);
+      } else
       block_fft<N, -1, T, NT, kWR>(rows, st, rows, tw, c);
     }
     if constexpr ((TV & 4) != 0) {
@@ -413,6 +454,30 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
     for (int i = 0; i < PE - 1; ++i) win[i] = win[i + NEW];
 #pragma unroll
     for (int i = 0; i < NEW; ++i) win[PE - 1 + i] = IN::cvt(pf[i]);
+    }
+  }
+  if constexpr (MOM) {
+    // the workgroup's sums in a fixed order: wave shuffles, then the four waves' values through
+    // LDS (behind a barrier: the last step's FFT rows live there), one lane stores the slot
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      mom[0] += __shfl_down(mom[0], off, 64);
+      mom[1] += __shfl_down(mom[1], off, 64);
+      mom[2] += __shfl_down(mom[2], off, 64);
+    }
+    static_assert(NT == 256, "four waves");
+    double* red = reinterpret_cast<double*>(smem);
+    __syncthreads();
+    if ((c & 63) == 0) {
+      red[(c >> 6) * 3 + 0] = mom[0];
+      red[(c >> 6) * 3 + 1] = mom[1];
+      red[(c >> 6) * 3 + 2] = mom[2];
+    }
+    __syncthreads();
+    if (c == 0) {
+      double* slot = a.mom + ((int64_t)pol * nw + w) * 3;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) slot[j] = (red[j] + red[3 + j]) + (red[6 + j] + red[9 + j]);
     }
   }
 }
@@ -453,6 +518,15 @@ template <int N, int P, int NU, int DE, class IN>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void analysis_stream_rt_dada_kernel(AnalysisArgs a) {
   const int w = a.linear ? (int)blockIdx.x : xcd_tile(blockIdx.x, gridDim.x);
   analysis_stream_body<N, P, NU, DE, 2, false, 0, 0, IN, OutDada32>(a, blockIdx.y, w, gridDim.x);
+}
+
+// The same kernel storing the plain cf32 product and summing its moments
+// (pfb_analysis_execute_quantised_to_dada, FUSED; AnalysisArgs::mom): every workgroup of the grid
+// writes its slot.  A kernel of its own name again (pfb_ana_stream_quant.hip instantiates them).
+template <int N, int P, int NU, int DE, bool LCBF, class IN>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void analysis_stream_moments_kernel(AnalysisArgs a) {
+  const int w = a.linear ? (int)blockIdx.x : xcd_tile(blockIdx.x, gridDim.x);
+  analysis_stream_body<N, P, NU, DE, 0, LCBF, 0, 0, IN, OutCf32, true>(a, blockIdx.y, w, gridDim.x);
 }
 
 // Workgroups per polarisation of a streaming launch, each a contiguous range of steps

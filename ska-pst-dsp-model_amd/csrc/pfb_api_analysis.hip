@@ -1,7 +1,8 @@
 // pfb_api_analysis.hip — the analysis half of the C ABI (include/pfb_api.h): the analysis plan
 // (tap padding and the tables computed in double, rounded once to float), the launch of one
 // analysis (analysis_run), pfb_analysis_execute* and the FilterBank stream object
-// (pfb_filterbank_*: carry-over buffers and kernel dispatch).
+// (pfb_filterbank_*: carry-over buffers and kernel dispatch), with their to-DADA and quantised
+// to-DADA forms (analysis_to_dada, analysis_quantised).
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -154,6 +155,28 @@ pfb_status pfb::host::analysis_run(pfb_analysis_plan* p, const AnaLaunch& l, hip
   }
   const double in_b = dd ? 2.0 * (dd->nbit / 8) : 8.0;  // bytes per input sample
   const double out_b = od ? 2.0 * (od->nbit / 8) : 8.0;  // bytes per output sample
+  if (l.moments) {
+    // the streaming kernel's moments instantiation: the plain product of all the call's rows
+    // (a LowCBF plan: its streaming shape, as launch_lowcbf sets it up)
+    if (od || l.z || l.lay || row0 != 0) return fail(PFB_ERR_UNSUPPORTED, "moments: the plain product only");
+    const bool lcbf = p->variant == pfb::kLowCbf;
+    pfb::AnalysisArgs a = analysis_args(p, l);
+    a.scratch = nullptr;
+    if (lcbf) {
+      a.variant = pfb::kBunton;
+      a.pad = l.pre ? l.pad : p->lowcbf_pad ? 1536 : 0;
+      a.pre_pol_stride = a.pad;
+      a.lcbf_scale = 4096.0f;
+    }
+    const int64_t slots = pfb::stream_moments_slots(a, lcbf);
+    if (slots <= 0) return fail(PFB_ERR_UNSUPPORTED, "moments: the plan is not on the streaming kernel");
+    HIPCHK(p->quant_mom.ensure((size_t)slots * 3 * sizeof(double)));
+    a.mom = p->quant_mom.as<double>();
+    ProfScope ps(0, (double)p->n_pol * (in_b * n_dat + 8.0 * K_end * p->C), s);
+    HIPCHK(pfb::launch_stream_moments(a, lcbf, s));
+    l.moments->slots = slots;
+    return PFB_OK;
+  }
   if (p->variant == pfb::kLowCbf) {
     pfb::LowCbfArgs c{};
     c.in = l.in;
@@ -297,7 +320,7 @@ static void analysis_host_tables(const pfb_analysis_desc* d, const pfb_analysis_
 
 static void analysis_release(pfb_analysis_plan* p) {
   for (DevBuf* b : {&p->taps, &p->twN, &p->zrev, &p->gtab, &p->scratch, &p->carry, &p->carry_next, &p->work, &p->stage_in,
-                    &p->stage_out, &p->dada_stage})
+                    &p->stage_out, &p->dada_stage, &p->quant_prod, &p->quant_mom, &p->quant_stats})
     b->release();
 }
 
@@ -382,7 +405,7 @@ extern "C" {
 // then only has to pass the checks
 static pfb_status analysis_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps, const DadaSection* sec,
                                 int64_t n_dat, pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out,
-                                int32_t mem, void* stream, const AnaOut* od = nullptr) {
+                                int32_t mem, void* stream, const AnaOut* od = nullptr, AnaMoments* mo = nullptr) {
   if (sec) in = static_cast<const pfb_cf32*>(sec->base);
   if (!p || (!in && n_dat > 0)) return fail(PFB_ERR_INVALID_ARG, "null argument");
   if (n_dat < 0) return fail(PFB_ERR_INVALID_ARG, "negative n_dat");
@@ -411,6 +434,7 @@ static pfb_status analysis_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_
   l.out_ps = out_ps;
   l.K_end = l.K_total = K;
   l.dada_out = od;
+  l.moments = mo;
   if (sec) {
     const AnaDada dd{sec->base, sec->nbit};
     if (section_fusable(p, *sec)) {
@@ -440,6 +464,7 @@ static pfb_status analysis_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_
   l.out = p->stage_out.as<float2>();
   l.out_ps = K * p->C;
   l.dada_out = nullptr;
+  l.moments = nullptr;
   pfb_status st = analysis_run(p, l, s);
   if (st != PFB_OK) return st;
   HIPCHK(copy_pols((float2*)out, out_ps, p->stage_out.as<float2>(), K * p->C, K * p->C, p->n_pol,
@@ -543,7 +568,7 @@ static pfb_status fb_carry(pfb_analysis_plan* p, pfb_analysis_plan::DevBuf& into
 static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps, int64_t n_in,
                                   pfb_cf32* out, int64_t out_ps, int64_t cap, int64_t* n_out, int32_t mem,
                                   void* stream, const OutLayout* lay, const DadaSection* sec = nullptr,
-                                  const AnaOut* od = nullptr) {
+                                  const AnaOut* od = nullptr, AnaMoments* mo = nullptr) {
   if (sec) {
     in = static_cast<const pfb_cf32*>(sec->base);
     in_ps = n_in;
@@ -576,6 +601,7 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
   l.K_end = Krun;
   l.K_total = K;
   l.dada_out = od;
+  l.moments = mo;
   {
     // Carry without the concatenation copy (streaming analysis kernel, device input): when
     // the new carry starts in the new input (input_idat >= B), ONE launch reads the new
@@ -637,7 +663,7 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
     // (a layout — pfb_filterbank_execute_strided on a padded plan; the Bunton plans it admits
     // take the streaming kernel above — goes straight to `out`: no scratch rows and no staging
     // buffer, fb_rows_dst)
-    if (!sec && !od && mem == PFB_MEM_DEVICE && B > 0 && !p->lowcbf_pad && p->fused && analysis_fused_carry_ok(p) &&
+    if (!sec && !od && !mo && mem == PFB_MEM_DEVICE && B > 0 && !p->lowcbf_pad && p->fused && analysis_fused_carry_ok(p) &&
         input_idat >= B && Kt > 0) {
       p->last_dada = last_dada;
       if (n_out) *n_out = Kt;
@@ -838,7 +864,10 @@ static pfb_status analysis_to_dada(pfb_analysis_plan* p, const pfb_cf32* in, int
       HIPCHK(pfb::launch_dada_pack_scaled(p->dada_stage.as<float2>(), K * p->C, rows, p->C, p->n_pol, out, nbit,
                                           scale, (hipStream_t)stream));
   }
-  if (st == PFB_OK) p->last_dada_out = fused ? PFB_DADA_OUTPUT_FUSED : PFB_DADA_OUTPUT_STAGED;
+  if (st == PFB_OK) {
+    p->last_dada_out = fused ? PFB_DADA_OUTPUT_FUSED : PFB_DADA_OUTPUT_STAGED;
+    p->last_quant = PFB_QUANTISER_NONE;
+  }
   return st;
 }
 
@@ -869,6 +898,131 @@ pfb_status pfb_filterbank_execute_dada_to_dada(pfb_analysis_plan* p, const void*
 }
 
 int32_t pfb_analysis_last_dada_output(const pfb_analysis_plan* p) { return p ? p->last_dada_out : -1; }
+
+// The quantised to-DADA calls (pfb_api.h): every check here, before the callee launches or
+// changes the stream state; the cf32 product into the plan's buffer — FUSED: by the streaming
+// kernel's moments instantiation, which leaves the partial sums; STAGED: by the plan's cf32 path,
+// then moments_partials_kernel — then the finish and the pack launch, all on the caller's stream.
+static pfb_status analysis_quantised(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps,
+                                     const DadaSection* sec_in, int64_t n, double rms, void* out, int32_t nbit,
+                                     float oscale, int64_t cap_bytes, int64_t* n_out, double* scale, void* stream,
+                                     bool stream_call) {
+  if (!p) return fail(PFB_ERR_INVALID_ARG, "null plan");
+  if (nbit != 8 && nbit != 16 && nbit != 32 && nbit != 64)
+    return fail(PFB_ERR_INVALID_ARG, "output NBIT must be 8, 16, 32 or 64");
+  if (!std::isfinite(oscale)) return fail(PFB_ERR_INVALID_ARG, "output scale is not finite");
+  if (!std::isfinite(rms)) return fail(PFB_ERR_INVALID_ARG, "quantiser rms is not finite");
+  if (reinterpret_cast<uintptr_t>(out) % (size_t)(nbit / 8) != 0)
+    return fail(PFB_ERR_INVALID_ARG, "output section not aligned to its NBIT");
+  if (sec_in) {
+    const pfb_status st = section_check(p, *sec_in, n);
+    if (st != PFB_OK) return st;
+  }
+  if (!(sec_in ? sec_in->base : (const void*)in) && n > 0) return fail(PFB_ERR_INVALID_ARG, "null argument");
+  if (n < 0) return fail(PFB_ERR_INVALID_ARG, "negative sample count");
+  if (!sec_in && in_ps < n) return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
+  // (K and rows: analysis_to_dada's)
+  const int64_t K = analysis_K(p, stream_call ? p->buffered + n : n);
+  const int64_t rows = stream_call ? K - (K % p->nu) : K;
+  if (n_out) *n_out = rows;
+  if (rows > 0) {
+    if (!out) return fail(PFB_ERR_INVALID_ARG, "null output");
+    const int64_t need = rows * p->C * p->n_pol * 2 * (nbit / 8);
+    if (cap_bytes < need)
+      return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld bytes", (long long)cap_bytes,
+                  (long long)need);
+  }
+  pfb::AnalysisArgs shape;
+  const bool fusable = section_kernel_shape(p, shape) && pfb::analysis_writes_dada(shape, 32);
+  if (p->quant_mode == PFB_QUANTISER_MOMENTS_FUSED && !fusable)
+    return fail(PFB_ERR_UNSUPPORTED, "quantiser moments FUSED: the plan is not on the streaming analysis kernel");
+  const bool fused = fusable && p->quant_mode != PFB_QUANTISER_MOMENTS_STAGED;
+  HIPCHK(hipSetDevice(p->device));
+  hipStream_t s = (hipStream_t)stream;
+  // all K computed rows have room (a padded stream call computes K and returns `rows`)
+  HIPCHK(p->quant_prod.ensure((size_t)p->n_pol * std::max<int64_t>(K, 1) * p->C * sizeof(float2)));
+  HIPCHK(p->quant_stats.ensure(4 * sizeof(double)));
+  AnaMoments mo;
+  AnaMoments* mp = fused && rms > 0 ? &mo : nullptr;
+  pfb_cf32* o = p->quant_prod.as<pfb_cf32>();
+  const pfb_status st =
+      stream_call ? filterbank_exec(p, in, in_ps, n, o, K * p->C, K, n_out, PFB_MEM_DEVICE, stream, nullptr, sec_in,
+                                    nullptr, mp)
+                  : analysis_exec(p, in, in_ps, sec_in, n, o, K * p->C, K, n_out, PFB_MEM_DEVICE, stream, nullptr, mp);
+  if (st != PFB_OK) return st;
+  if (scale) *scale = 1.0;
+  if (rows > 0) {
+    const float2* prod = p->quant_prod.as<float2>();
+    const int64_t cnt = rows * p->C;  // per polarisation
+    const double* stats = nullptr;
+    if (rms > 0) {
+      int64_t slots = mo.slots;
+      if (!mp) {
+        slots = pfb::moments_partials_slots(cnt, p->n_pol);
+        HIPCHK(p->quant_mom.ensure((size_t)slots * 3 * sizeof(double)));
+        HIPCHK(pfb::launch_moments_partials(prod, K * p->C, cnt, p->n_pol, p->quant_mom.as<double>(), s));
+      }
+      HIPCHK(pfb::launch_moments_finish(p->quant_mom.as<double>(), slots, (double)cnt * p->n_pol, rms,
+                                        p->quant_stats.as<double>(), s));
+      stats = p->quant_stats.as<double>();
+    }
+    HIPCHK(pfb::launch_quantise_pack(prod, K * p->C, cnt, p->n_pol, stats, oscale, out, nbit, s));
+    if (scale && stats) {
+      HIPCHK(hipMemcpyAsync(scale, stats + 3, sizeof(double), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+    }
+  }
+  p->last_quant = fused ? PFB_QUANTISER_FUSED : PFB_QUANTISER_STAGED;
+  p->last_dada_out = PFB_DADA_OUTPUT_NONE;
+  return PFB_OK;
+}
+
+pfb_status pfb_analysis_execute_quantised_to_dada(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps,
+                                                  int64_t n_dat, double rms, void* out, int32_t out_nbit,
+                                                  float out_scale, int64_t cap_bytes, int64_t* n_out, double* scale,
+                                                  void* stream) {
+  return analysis_quantised(p, in, in_ps, nullptr, n_dat, rms, out, out_nbit, out_scale, cap_bytes, n_out, scale,
+                            stream, false);
+}
+
+pfb_status pfb_filterbank_execute_quantised_to_dada(pfb_analysis_plan* p, const pfb_cf32* in, int64_t in_ps,
+                                                    int64_t n_in, double rms, void* out, int32_t out_nbit,
+                                                    float out_scale, int64_t cap_bytes, int64_t* n_out, double* scale,
+                                                    void* stream) {
+  return analysis_quantised(p, in, in_ps, nullptr, n_in, rms, out, out_nbit, out_scale, cap_bytes, n_out, scale,
+                            stream, true);
+}
+
+pfb_status pfb_analysis_execute_dada_quantised_to_dada(pfb_analysis_plan* p, const void* in, int32_t nbit,
+                                                       int32_t ndim, int32_t order, int64_t n_dat, double rms,
+                                                       void* out, int32_t out_nbit, float out_scale,
+                                                       int64_t cap_bytes, int64_t* n_out, double* scale,
+                                                       void* stream) {
+  const DadaSection sec{in, nbit, ndim, order};
+  return analysis_quantised(p, nullptr, 0, &sec, n_dat, rms, out, out_nbit, out_scale, cap_bytes, n_out, scale,
+                            stream, false);
+}
+
+pfb_status pfb_filterbank_execute_dada_quantised_to_dada(pfb_analysis_plan* p, const void* in, int32_t nbit,
+                                                         int32_t ndim, int32_t order, int64_t n_in, double rms,
+                                                         void* out, int32_t out_nbit, float out_scale,
+                                                         int64_t cap_bytes, int64_t* n_out, double* scale,
+                                                         void* stream) {
+  const DadaSection sec{in, nbit, ndim, order};
+  return analysis_quantised(p, nullptr, 0, &sec, n_in, rms, out, out_nbit, out_scale, cap_bytes, n_out, scale,
+                            stream, true);
+}
+
+pfb_status pfb_analysis_set_quantiser_moments(pfb_analysis_plan* p, int32_t mode) {
+  if (!p) return fail(PFB_ERR_INVALID_ARG, "null plan");
+  if (mode != PFB_QUANTISER_MOMENTS_AUTO && mode != PFB_QUANTISER_MOMENTS_FUSED &&
+      mode != PFB_QUANTISER_MOMENTS_STAGED)
+    return fail(PFB_ERR_INVALID_ARG, "unknown quantiser moments mode %d", mode);
+  p->quant_mode = mode;
+  return PFB_OK;
+}
+
+int32_t pfb_analysis_last_quantiser(const pfb_analysis_plan* p) { return p ? p->last_quant : -1; }
 
 
 int64_t pfb_filterbank_buffered(const pfb_analysis_plan* p) { return p ? p->buffered : -1; }

@@ -178,6 +178,12 @@ struct pfb_analysis_plan {
   int last_dada = PFB_DADA_INPUT_NONE;  // pfb_analysis_last_dada_input
   int last_dada_out = PFB_DADA_OUTPUT_NONE;  // pfb_analysis_last_dada_output
   DevBuf dada_stage;  // STAGED DADA output: the cf32 product before its scaled pack launch
+  // the quantised output (pfb_analysis_execute_quantised_to_dada): the cf32 product the pack
+  // launch reads, the moments' partial sums (three doubles per slot) and the 32-byte stats block
+  // {sum re, sum im, s2, scale} — the plan's own, grown with the call's length
+  DevBuf quant_prod, quant_mom, quant_stats;
+  int quant_mode = PFB_QUANTISER_MOMENTS_AUTO;  // pfb_analysis_set_quantiser_moments
+  int last_quant = PFB_QUANTISER_NONE;          // pfb_analysis_last_quantiser
   // round trip (pfb_roundtrip_execute): the analysis runs on this stream, ahead of the
   // synthesis on the caller's stream; one event per chunk orders them
   hipStream_t aux = nullptr;
@@ -222,6 +228,11 @@ namespace pfb::host {
 template <class Plan>
 pfb_status cf32_output(Plan* p, pfb_status st) {
   if (p && st == PFB_OK) p->last_dada_out = PFB_DADA_OUTPUT_NONE;
+  return st;
+}
+// (an analysis plan: pfb_analysis_last_quantiser reports NONE as well)
+inline pfb_status cf32_output(pfb_analysis_plan* p, pfb_status st) {
+  if (p && st == PFB_OK) p->last_dada_out = PFB_DADA_OUTPUT_NONE, p->last_quant = PFB_QUANTISER_NONE;
   return st;
 }
 
@@ -271,6 +282,13 @@ struct AnaOut {
   float scale;
 };
 
+// The launch also sums the moments of the product it stores (the streaming kernel's moments
+// instantiation, FUSED quantised output): analysis_run sizes the plan's quant_mom for the
+// launch's grid and reports the slots it wrote (0: nothing launched)
+struct AnaMoments {
+  int64_t slots = 0;
+};
+
 // One analysis launch (analysis_run); a call site sets the members it uses.
 struct AnaLaunch {
   // input: n_dat samples per pol from `in`, which starts `pad` samples into the series (a read
@@ -298,6 +316,8 @@ struct AnaLaunch {
   // the launch writes the section instead of `out`, which is ignored
   // (analysis_dada_out_fusable plans only)
   const AnaOut* dada_out = nullptr;
+  // the launch stores the plain cf32 product and its moments (streaming-kernel plans only)
+  AnaMoments* moments = nullptr;
 };
 
 pfb_status analysis_run(pfb_analysis_plan* p, const AnaLaunch& l, hipStream_t s);

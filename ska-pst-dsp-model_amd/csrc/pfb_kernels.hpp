@@ -118,6 +118,10 @@ struct AnalysisArgs {
   void* dout = nullptr;
   int dout_nbit = 0;
   float dout_scale = 1.f;
+  // The moments of the product (analysis_stream_moments_kernel, launch_stream_moments): workgroup
+  // w of polarisation p of a grid of nw per polarisation stores (sum re, sum im, sum re^2 + im^2)
+  // of the values it stored, in double, at mom[(p nw + w) 3 ...]
+  double* mom = nullptr;
 };
 // the plan's kernel has a loader for such a section (the streaming kernel; the LDS-shared FIR
 // of the N > 256 path, launches without stage-1 rows)
@@ -130,6 +134,24 @@ hipError_t launch_stream_dadaout(const AnalysisArgs& a, bool lcbf, hipStream_t s
 // those kernels read a DADA section of in_nbit in place when they write out_nbit (the same
 // NBIT, or any integer NBIT into NBIT 32); other pairs come in unpacked, as cf32
 bool dadaout_reads_dada(int in_nbit, int out_nbit);
+// The quantised output (pfb_ana_stream_quant.hip; pfb_analysis_execute_quantised_to_dada).
+// The streaming kernel storing its cf32 product and the product's moments (AnalysisArgs::mom);
+// lcbf: the LowCBF instantiation.  stream_moments_slots: the n_pol x nw slots of three doubles
+// the launch of `a` writes (-1: no such kernel), for the caller to size `mom` and to finish.
+int64_t stream_moments_slots(const AnalysisArgs& a, bool lcbf);
+hipError_t launch_stream_moments(const AnalysisArgs& a, bool lcbf, hipStream_t s);
+// The same slots from a stored product x[pol][0, n) (pol stride ps, both even; 16-B aligned): one
+// slot per workgroup of a one-shot grid.  moments_partials_slots: their number.
+int64_t moments_partials_slots(int64_t n, int n_pol);
+hipError_t launch_moments_partials(const float2* x, int64_t ps, int64_t n, int n_pol, double* mom, hipStream_t s);
+// stats = {sum re, sum im, sum re^2 + im^2, scale}: the slots added in index order by one
+// workgroup, scale = rms / sqrt(var), var = (s2 - (sum re^2 + sum im^2) / cnt) / (cnt - 1)
+hipError_t launch_moments_finish(const double* mom, int64_t slots, double cnt, double rms, double* stats,
+                                 hipStream_t s);
+// x[pol][0, n) -> the TFP section `out` of n x n_pol complex samples of nbit 8 / 16 / 32 / 64:
+// each component to_sample(out_scale * roundf(sf * x)), sf = (float)stats[3] or 1 (stats null)
+hipError_t launch_quantise_pack(const float2* x, int64_t ps, int64_t n, int n_pol, const double* stats,
+                                float out_scale, void* out, int nbit, hipStream_t s);
 // The file-to-file round trip's analysis launch (pfb_ana_stream_rtdada.hip): the streaming
 // kernel reading the section `din` (in_nbit 8 / 16 / 32) in place, storing the product as the
 // NBIT 32 float section `dout` (dout_scale 1) and the stage-1 rows z in 2-row runs (zblk 2) —

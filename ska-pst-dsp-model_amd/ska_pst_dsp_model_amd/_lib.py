@@ -47,6 +47,12 @@ PFB_DADA_INPUT_STAGED = 2
 PFB_DADA_OUTPUT_NONE = 0
 PFB_DADA_OUTPUT_FUSED = 1
 PFB_DADA_OUTPUT_STAGED = 2
+PFB_QUANTISER_MOMENTS_AUTO = 0
+PFB_QUANTISER_MOMENTS_FUSED = 1
+PFB_QUANTISER_MOMENTS_STAGED = 2
+PFB_QUANTISER_NONE = 0
+PFB_QUANTISER_FUSED = 1
+PFB_QUANTISER_STAGED = 2
 PFB_STRIDED_INPUT_NONE = 0
 PFB_STRIDED_INPUT_IN_PLACE = 1
 PFB_STRIDED_INPUT_STAGED = 2
@@ -146,6 +152,22 @@ SYMBOLS = [
                                                       c_void_p, c_int32, c_float, c_int64, POINTER(c_int64),
                                                       c_void_p]),
     ("pfb_analysis_last_dada_output", c_int32, [c_void_p]),
+    ("pfb_analysis_execute_quantised_to_dada", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_double,
+                                                         c_void_p, c_int32, c_float, c_int64, POINTER(c_int64),
+                                                         POINTER(c_double), c_void_p]),
+    ("pfb_filterbank_execute_quantised_to_dada", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_double,
+                                                           c_void_p, c_int32, c_float, c_int64, POINTER(c_int64),
+                                                           POINTER(c_double), c_void_p]),
+    ("pfb_analysis_execute_dada_quantised_to_dada", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                                              c_int64, c_double, c_void_p, c_int32, c_float,
+                                                              c_int64, POINTER(c_int64), POINTER(c_double),
+                                                              c_void_p]),
+    ("pfb_filterbank_execute_dada_quantised_to_dada", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                                                c_int64, c_double, c_void_p, c_int32, c_float,
+                                                                c_int64, POINTER(c_int64), POINTER(c_double),
+                                                                c_void_p]),
+    ("pfb_analysis_set_quantiser_moments", c_int32, [c_void_p, c_int32]),
+    ("pfb_analysis_last_quantiser", c_int32, [c_void_p]),
     ("pfb_synthesis_execute_to_dada", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                                 c_int32, c_float, c_int64, POINTER(c_int64), c_void_p]),
     ("pfb_inverse_filterbank_execute_to_dada", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p,

@@ -18,7 +18,7 @@ goes through the HIP kernels of ``libpfb_hip.so``; there is no CPU fallback.
 from __future__ import annotations
 
 import hashlib
-from ctypes import byref, c_int64, c_void_p
+from ctypes import byref, c_double, c_int64, c_void_p
 
 import numpy as np
 
@@ -129,6 +129,7 @@ def _order(lowcbf: bool) -> int:
 # what the plans' last_* getters report (anything else, 0 and -1 included: 'none')
 _DADA_INPUT_NAMES = {_lib.PFB_DADA_INPUT_FUSED: "fused", _lib.PFB_DADA_INPUT_STAGED: "staged"}
 _DADA_OUTPUT_NAMES = {_lib.PFB_DADA_OUTPUT_FUSED: "fused", _lib.PFB_DADA_OUTPUT_STAGED: "staged"}
+_QUANTISER_NAMES = {_lib.PFB_QUANTISER_FUSED: "fused", _lib.PFB_QUANTISER_STAGED: "staged"}
 _STRIDED_INPUT_NAMES = {_lib.PFB_STRIDED_INPUT_IN_PLACE: "in_place",
                         _lib.PFB_STRIDED_INPUT_STAGED: "staged"}
 _STAGE1_NAMES = {_lib.PFB_STAGE1_STORED: "stored", _lib.PFB_STAGE1_RECOMPUTED: "recomputed"}
@@ -382,6 +383,68 @@ class AnalysisPlan(_Plan):
         stored the file's own bytes), 'staged' (the cf32 product packed by a second launch),
         'none' (no such call, or a cf32-output call since) — pfb_analysis_last_dada_output."""
         return _mode_name(self, "pfb_analysis_last_dada_output", _DADA_OUTPUT_NAMES)
+
+    def _quantised(self, fn, src, head: tuple, n_dat: int, out_nbit: int, rms: float, scale: float,
+                   stateful: bool, return_scale: bool):
+        """The shared tail of the quantised to-DADA calls: the section of ``_section_rows``
+        rows, the call, and the quantiser's scale when asked for (the call then waits)."""
+        sec, nbytes = _alloc_section((self._section_rows(n_dat, stateful), self.out_chan, self.n_pol, 2),
+                                     out_nbit, src.device)
+        n_out = c_int64(0)
+        got = c_double(1.0)
+        _lib.check(fn(self._h, c_void_p(src.data_ptr()), *head, n_dat, float(rms), c_void_p(sec.data_ptr()),
+                      int(out_nbit), float(scale), nbytes, byref(n_out),
+                      byref(got) if return_scale else None, _stream_of(src, self)))
+        _keep_alive(self, src, src.device)
+        sec = sec[:n_out.value]
+        return (sec, float(got.value)) if return_scale else sec
+
+    def execute_quantised_to_dada(self, x, nbit: int, rms: float, scale: float = 1.0, stateful: bool = False,
+                                  return_scale: bool = False):
+        """The FilterBank's rms-scaled, rounded product written as a DADA data section
+        (FilterBank.m:106-113, then the file's cast): with ``y = execute(x)`` and
+        ``s = rms / std(y)`` (1 when ``rms <= 0``), bit for bit
+        ``layout.dada_pack(float32(scale) * round(float32(s) * y), nbit)`` — the moments summed by
+        the analysis kernel and one pass over the product where the plan is on the streaming
+        kernel (pfb_analysis_execute_quantised_to_dada / pfb_filterbank_execute_quantised_to_dada;
+        ``last_quantiser()`` tells).  Shapes and dtypes as ``execute_to_dada``; with
+        ``return_scale`` -> (section, s), and the call waits for the device."""
+        if not is_device_array(x):
+            raise _lib.PfbError(_lib.PFB_ERR_INVALID_ARG, "execute_quantised_to_dada: expects a device tensor")
+        x, _ = self._prep_in(x)
+        if x.shape[0] != self.n_pol:
+            raise ValueError(f"plan built for n_pol={self.n_pol}, got {x.shape[0]}")
+        n_dat = x.shape[1]
+        fn = self._lib.pfb_filterbank_execute_quantised_to_dada if stateful else \
+            self._lib.pfb_analysis_execute_quantised_to_dada
+        return self._quantised(fn, x, (n_dat,), n_dat, nbit, rms, scale, stateful, return_scale)
+
+    def execute_dada_quantised_to_dada(self, raw, in_nbit: int, out_nbit: int, rms: float, scale: float = 1.0,
+                                       ndim: int = 2, lowcbf: bool = False, stateful: bool = False,
+                                       return_scale: bool = False):
+        """``execute_quantised_to_dada`` of a single-channel DADA data section, read as
+        ``execute_dada`` reads it (pfb_analysis_execute_dada_quantised_to_dada /
+        pfb_filterbank_execute_dada_quantised_to_dada)."""
+        raw, n_dat = _section(raw, "execute_dada_quantised_to_dada", self.n_pol, in_nbit, ndim, lowcbf)
+        fn = self._lib.pfb_filterbank_execute_dada_quantised_to_dada if stateful else \
+            self._lib.pfb_analysis_execute_dada_quantised_to_dada
+        return self._quantised(fn, raw, (int(in_nbit), int(ndim), _order(lowcbf)), n_dat, out_nbit, rms, scale,
+                               stateful, return_scale)
+
+    def set_quantiser_moments(self, mode: str):
+        """Where the quantised calls take the product's moments: 'auto' (in the analysis kernel
+        where the plan is on the streaming kernel), 'fused' (there or PFB_ERR_UNSUPPORTED),
+        'staged' (always from the stored product) — pfb_analysis_set_quantiser_moments."""
+        modes = {"auto": _lib.PFB_QUANTISER_MOMENTS_AUTO, "fused": _lib.PFB_QUANTISER_MOMENTS_FUSED,
+                 "staged": _lib.PFB_QUANTISER_MOMENTS_STAGED}
+        if mode not in modes:
+            raise ValueError(f"quantiser moments mode {mode!r}: one of {sorted(modes)}")
+        _lib.check(self._lib.pfb_analysis_set_quantiser_moments(self._h, modes[mode]))
+
+    def last_quantiser(self) -> str:
+        """The path of the plan's last quantised to-DADA call: 'fused', 'staged', or 'none' (no
+        such call, or another execute call since) — pfb_analysis_last_quantiser."""
+        return _mode_name(self, "pfb_analysis_last_quantiser", _QUANTISER_NAMES)
 
 
 # ============================================================================ synthesis

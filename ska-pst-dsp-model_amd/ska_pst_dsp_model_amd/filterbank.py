@@ -74,7 +74,7 @@ def _quantize(x, rms, device=0):
 class FilterBank(Channelizer):
     """FilterBank.m:1-130 — analysis PFB with input buffering and nu-trimming."""
 
-    def __init__(self, config=None, n_pol: int = None, device: int = 0):
+    def __init__(self, config=None, n_pol: int = None, device: int = 0, fused_quantiser: bool = None):
         self.pfb_analysis = "polyphase_analysis"
         self.os_factor = None
         self.filt_coeff = None
@@ -83,6 +83,9 @@ class FilterBank(Channelizer):
         self.rmsInput = 0.0
         self.rndOutput = False
         self.rmsOutput = 0.0
+        # opt-in: the to-DADA calls take the output quantiser through the plan's quantised
+        # calls (AnalysisPlan.execute_quantised_to_dada) instead of the execute fallback
+        self.fused_quantiser = False
         self.device = device
         self._plan = None
         self._n_pol = n_pol
@@ -95,6 +98,14 @@ class FilterBank(Channelizer):
             self.rmsInput = float(_cfg(config, "rmsInput", 0.0))
             self.rndOutput = bool(_cfg(config, "rndOutput", False))
             self.rmsOutput = float(_cfg(config, "rmsOutput", 0.0))
+            self.fused_quantiser = bool(_cfg(config, "fused_quantiser", False))
+        if fused_quantiser is not None:
+            self.fused_quantiser = bool(fused_quantiser)
+
+    def _quantiser_fused(self) -> bool:
+        """The to-DADA calls take the plan's quantised calls: opted in, the output quantiser
+        configured and no input quantiser (whose scale needs the whole input first)."""
+        return bool(self.fused_quantiser and self.rndOutput and not self.rndInput)
 
     def _ensure_plan(self, n_pol):
         if self._plan is None or self._plan.n_pol != n_pol:
@@ -142,7 +153,13 @@ class FilterBank(Channelizer):
         output, and the same carry (``AnalysisPlan.execute_to_dada``).  With ``rndInput``,
         ``rndOutput`` or ``rmsOutput`` configured the quantiser's scale needs the variance of
         the whole input or output (FilterBank.m:75-83,106-113): the call then takes
-        ``execute`` followed by ``layout.dada_pack``."""
+        ``execute`` followed by ``layout.dada_pack`` — unless ``fused_quantiser`` is set, which
+        sends the ``rndOutput`` case (without ``rndInput``) through
+        ``AnalysisPlan.execute_quantised_to_dada`` with ``rms = rmsOutput``: the moments summed
+        by the analysis kernel, one pass over the product."""
+        if self._quantiser_fused():
+            plan = self._ensure_plan(_npol(input))
+            return self, plan.execute_quantised_to_dada(input, nbit, self.rmsOutput, scale=scale, stateful=True)
         if self.rndInput or self.rndOutput or self.rmsOutput:
             _, view = self.execute(input)
             return self, self._pack_view(view, nbit, scale)
@@ -153,7 +170,11 @@ class FilterBank(Channelizer):
                              n_pol: int = 1):
         """``execute_dada`` written as a DADA data section like ``execute_to_dada``: file
         bytes in, file bytes out (``AnalysisPlan.execute_dada_to_dada``), with the same
-        fallbacks for the quantisation hooks."""
+        fallbacks for the quantisation hooks (and the same ``fused_quantiser`` path)."""
+        if self._quantiser_fused():
+            plan = self._ensure_plan(int(n_pol))
+            return self, plan.execute_dada_quantised_to_dada(raw, in_nbit, out_nbit, self.rmsOutput, scale=scale,
+                                                             ndim=ndim, stateful=True)
         if self.rndInput or self.rndOutput or self.rmsOutput:
             _, view = self.execute_dada(raw, in_nbit, ndim=ndim, n_pol=n_pol)
             return self, self._pack_view(view, out_nbit, scale)
