@@ -578,6 +578,64 @@ pfb_status pfb_filterbank_execute_dada_quantised_to_dada(pfb_analysis_plan* plan
 pfb_status pfb_analysis_set_quantiser_moments(pfb_analysis_plan* plan, int32_t mode);
 int32_t pfb_analysis_last_quantiser(const pfb_analysis_plan* plan);
 
+/* The FilterBank's quantised input (FilterBank.m:75-83: scale = rmsInput / sqrt(var(input, 0,
+ * "all")), input = round(scale * input), before the carried samples are put in front): a property
+ * of the analysis plan, off by default.  pfb_analysis_set_input_quantiser(plan, enable, rms)
+ * turns it on (enable != 0) or off; with it on, every execute entry below replaces its own new
+ * samples x — the n_dat or n_in samples of every polarisation, cnt = samples * n_pol; for a DADA
+ * section the exactly cast integers or floats — by
+ *   q = roundf((float)scale * x)   per component (pfb_quantize's operation: half away from zero)
+ * before anything else sees them, with
+ *   scale = rms / sqrt(var),  var = (sum |x|^2 - ((sum re)^2 + (sum im)^2) / cnt) / (cnt - 1)
+ * summed in double.  rms <= 0: round only (the scale is 1, no moments are taken).  Carried
+ * samples are not rounded again — they were rounded in the call that brought them — and do not
+ * enter the variance, nor do the LowCBF pre-padding zeros.  The carry a call leaves holds rounded
+ * values at that call's scale, also when the call completes no row.  rms > 0 with cnt < 2 (one
+ * sample): PFB_ERR_INVALID_ARG, as in pfb_quantize; a call with no samples takes scale 1.  A
+ * non-finite rms or a null plan: PFB_ERR_INVALID_ARG.  A zero variance is not special-cased and
+ * is not compared with anything.  The setters may be called at any time, also with samples
+ * buffered; they take effect at the next call and touch no device state.
+ * Result: everything else about the call is that of the same call on q with the quantiser off,
+ * bit for bit — outputs, *n_out, status codes, pfb_filterbank_buffered, the carry,
+ * pfb_analysis_last_dada_output, pfb_analysis_last_quantiser and the LowCBF pending pre-padding;
+ * pfb_analysis_last_dada_input reports how the section's bytes were read (STAGED when the
+ * quantising copy unpacked them).  Every check still runs before any launch or state change.
+ * Entries: pfb_analysis_execute, pfb_filterbank_execute (device and host memory),
+ * pfb_filterbank_execute_strided, the _dada, _to_dada and _dada_to_dada calls and the four
+ * _quantised_to_dada calls.  pfb_roundtrip_execute* with such a plan: PFB_ERR_UNSUPPORTED,
+ * nothing launched.
+ * FUSED: a plan on the streaming kernel whose call reads its new samples in place (cf32 device
+ * memory, or a section pfb_analysis_execute_dada fuses) and whose product goes out as cf32 or
+ * through the moments kernel of the quantised output: one pass over the new samples for
+ * per-workgroup partial sums (ordinary stores), one workgroup that adds them in a fixed order and
+ * forms the scale, then the analysis launch, which rounds each sample as it loads it.
+ * STAGED: everything else — padded plans, the one-launch N <= 256 kernel, FIR + row FFT, host
+ * memory, strided and plain _to_dada launches, a stream call that concatenates its carry, a
+ * section the kernel does not read in place, and mode STAGED: the same two moments launches,
+ * then a quantising copy of the new samples into a buffer of the plan (behind the carry in the
+ * concatenation buffer where the call concatenates), and the plan's ordinary path on it.
+ * pfb_analysis_set_input_quantiser_mode (pfb_quantiser_moments: AUTO, the default, takes FUSED
+ * where the call allows it; FUSED on a call that cannot take it: PFB_ERR_UNSUPPORTED from that
+ * call, nothing launched; STAGED).  pfb_analysis_last_input_quantiser: the path of the plan's
+ * last call, NONE with the quantiser off or before any call, -1 for a null plan.
+ * pfb_analysis_last_input_scale copies the last call's scale back on the given stream and
+ * synchronises it (1 for a round-only call or one without samples) — the only thing here that
+ * waits for the device.
+ * The partial sums and the 32-byte block {sum re, sum im, sum |x|^2, scale} belong to the plan,
+ * apart from the output quantiser's (both can be live in one call); they grow only with the
+ * call's length, nothing is per device or per stream.  The setters and a call can be captured
+ * into a graph after one call of that length.  No floating-point atomics: the same plan, input
+ * and grid give the same scale bits and the same bytes.  (Measured: DESIGN.md §4.12.) */
+typedef enum pfb_input_quantiser {
+  PFB_INPUT_QUANTISER_NONE = 0,
+  PFB_INPUT_QUANTISER_FUSED = 1,
+  PFB_INPUT_QUANTISER_STAGED = 2
+} pfb_input_quantiser;
+pfb_status pfb_analysis_set_input_quantiser(pfb_analysis_plan* plan, int32_t enable, double rms);
+pfb_status pfb_analysis_set_input_quantiser_mode(pfb_analysis_plan* plan, int32_t mode);
+int32_t pfb_analysis_last_input_quantiser(const pfb_analysis_plan* plan);
+pfb_status pfb_analysis_last_input_scale(pfb_analysis_plan* plan, double* scale, void* stream);
+
 /* Synthesis writing its output straight into a DADA data section (polyphase_synthesis /
  * InverseFilterBank.m:92-96 followed by write_dada_data.m:32-50): the single-channel TFP
  * section, NDIM 2, out_nbit 8 / 16 (integers), 32 (float) or 64 (double).  Device memory only.

@@ -25,6 +25,10 @@ one MI355X, as algorithmic HBM bytes / time against the 8 TB/s peak.
     C2 shape, what the object enqueues today (execute, pfb_quantize, the copy, pfb_dada_pack)
     against pfb_analysis_execute_quantised_to_dada in AUTO and in STAGED mode and the plain
     pfb_analysis_execute_to_dada as the floor, interleaved
+  * --only-quantised-input: the FilterBank's rms-scaled, rounded input at the C2 shape, what the
+    object enqueues today (pfb_dada_unpack, pfb_quantize, pfb_analysis_execute) against the same
+    call with the plan's input quantiser in AUTO and in STAGED mode and with the quantiser off as
+    the floor, interleaved
   * --only-twostage-inverse: TwoStageInverseFilterBank with the channel gather against the
     strided input (pfb_inverse_filterbank_execute_strided), interleaved
 
@@ -81,6 +85,10 @@ def main():
     ap.add_argument("--only-quantised-output", action="store_true",
                     help="the quantised_output A/B alone (--reps: calls per timed window, at least 20; "
                          "--rounds: windows, at least 9)")
+    ap.add_argument("--only-quantised-input", action="store_true",
+                    help="the quantised_input A/B alone (--reps: calls per timed window, at least 20; "
+                         "--rounds: windows, at least 9; --sides A: side A alone, for the parent commit's library)")
+    ap.add_argument("--sides", default="A,B,Bs,floor", help="with --only-quantised-input: the sides to run")
     ap.add_argument("--only-twostage-inverse", action="store_true",
                     help="the inverse cascade's gather vs strided-input A/B alone (--reps: calls per window)")
     ap.add_argument("--rounds", type=int, default=15,
@@ -127,6 +135,9 @@ def main():
         return dada_roundtrip(torch, pfb, dev, max(args.reps, 20), args.rounds)
     if args.only_quantised_output:
         return quantised_output(torch, pfb, dev, max(args.reps, 20), max(args.rounds, 9))
+    if args.only_quantised_input:
+        return quantised_input(torch, pfb, dev, max(args.reps, 20), max(args.rounds, 9),
+                               tuple(args.sides.split(",")))
     if args.only_twostage_inverse:
         return twostage_inverse(torch, pfb, noise, max(args.reps, 20), max(args.rounds, 5))
     # ---- C2' (4/3) round trip
@@ -630,6 +641,135 @@ def quantised_output(torch, pfb, dev, reps, rounds, sides=("A", "A_nocopy", "B",
                 print(json.dumps(rec), flush=True)
                 del plan, src, cf, quant, copy, sec
                 torch.cuda.empty_cache()
+
+
+def quantised_input(torch, pfb, dev, reps, rounds, sides=("A", "B", "Bs", "floor")):
+    """The FilterBank's input quantiser (FilterBank.m:75-83) at the C2 shape (256 ch, 8/7, 2^24
+    samples), through the C ABI into preallocated buffers.
+    A: what FilterBank enqueues today — pfb_dada_unpack for an NBIT 16 section, pfb_quantize(rms)
+    into a buffer, pfb_analysis_execute.  B: the call with the plan's input quantiser, AUTO.  Bs:
+    the same, STAGED.  floor: the same call with the quantiser off.  The cells: cf32 and NBIT 16
+    input, one and two polarisations, cf32 output — and one pfb_analysis_execute_dada_quantised_to_dada
+    cell (NBIT 16 in and out, both quantisers; its A: unpack, pfb_quantize, execute, pfb_quantize,
+    pfb_dada_pack).  `sides`: "A" alone runs on a library without the new entry points (the
+    parent commit's, the yardstick).  All sides are warmed, then `rounds` windows of `reps` calls
+    of each side, alternating in one process; one line per cell with the median, min, max and
+    max - min of each side, whether A's and B's outputs are equal and their float32 scales have
+    the same bits, the byte totals from the formulas, and the project's rule: the lower median wins
+    when the difference exceeds the larger spread."""
+    from ctypes import byref, c_double, c_int64, c_void_p
+    from ska_pst_dsp_model_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator(device=dev).manual_seed(10)
+    taps = pfb.design_PFB_FIR_filter(256, "8/7", 12)
+    n, N, rms = 1 << 24, 256, 20.0
+    AUTO, STAGED = _lib.PFB_QUANTISER_MOMENTS_AUTO, _lib.PFB_QUANTISER_MOMENTS_STAGED
+    cells = [(in_nbit, n_pol, 0) for in_nbit in (0, 16) for n_pol in (1, 2)] + [(16, 1, 16)]
+    for in_nbit, n_pol, out_nbit in cells:
+        plan = pfb.AnalysisPlan(taps, N, "8/7", "polyphase_analysis", n_pol)
+        K, C = plan.output_length(n), plan.out_chan
+        if in_nbit:
+            src = (torch.randn((n * n_pol * 2,), device=dev, generator=g) * 1500 + 400).to(torch.int16)
+            unp = torch.empty((n_pol, n), dtype=torch.complex64, device=dev)
+        else:
+            src = torch.view_as_complex(torch.randn((n_pol, n, 2), device=dev, generator=g) + 0.25)
+            unp = src
+        qbuf = torch.empty((n_pol, n), dtype=torch.complex64, device=dev)
+        cf = torch.empty((n_pol, K, C), dtype=torch.complex64, device=dev)
+        if out_nbit:
+            quant = torch.empty_like(cf)
+            out = {k: torch.empty((K, C, n_pol, 2), dtype=torch.int16, device=dev) for k in sides}
+            nbytes = K * C * n_pol * 2 * (out_nbit // 8)
+        else:
+            out = {k: (cf if k == "A" else torch.empty_like(cf)) for k in sides}
+        stream = c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        n_out = c_int64(0)
+
+        def side_a(scale=None):
+            if in_nbit:
+                _lib.check(lib.pfb_dada_unpack(c_void_p(src.data_ptr()), in_nbit, 2, _lib.PFB_DADA_TFP, n, 1, n_pol,
+                                               c_void_p(unp.data_ptr()), n, stream))
+            _lib.check(lib.pfb_quantize(c_void_p(unp.data_ptr()), n, n, n_pol, rms, c_void_p(qbuf.data_ptr()), n,
+                                        scale, stream))
+            _lib.check(lib.pfb_analysis_execute(plan._h, c_void_p(qbuf.data_ptr()), n, n, c_void_p(cf.data_ptr()),
+                                                K * C, K, byref(n_out), _lib.PFB_MEM_DEVICE, stream))
+            if out_nbit:
+                _lib.check(lib.pfb_quantize(c_void_p(cf.data_ptr()), K * C, K * C, n_pol, 3000.0,
+                                            c_void_p(quant.data_ptr()), K * C, None, stream))
+                _lib.check(lib.pfb_dada_pack(c_void_p(quant.data_ptr()), K * C, K, C, n_pol,
+                                             c_void_p(out["A"].data_ptr()), out_nbit, stream))
+
+        def new_call(key, on, mode):
+            _lib.check(lib.pfb_analysis_set_input_quantiser(plan._h, int(on), rms))
+            _lib.check(lib.pfb_analysis_set_input_quantiser_mode(plan._h, mode))
+            dst = c_void_p(out[key].data_ptr())
+            if out_nbit:
+                _lib.check(lib.pfb_analysis_execute_dada_quantised_to_dada(
+                    plan._h, c_void_p(src.data_ptr()), in_nbit, 2, _lib.PFB_DADA_TFP, n, 3000.0, dst, out_nbit, 1.0,
+                    nbytes, byref(n_out), None, stream))
+            elif in_nbit:
+                _lib.check(lib.pfb_analysis_execute_dada(plan._h, c_void_p(src.data_ptr()), in_nbit, 2,
+                                                         _lib.PFB_DADA_TFP, n, dst, K * C, K, byref(n_out), stream))
+            else:
+                _lib.check(lib.pfb_analysis_execute(plan._h, c_void_p(src.data_ptr()), n, n, dst, K * C, K,
+                                                    byref(n_out), _lib.PFB_MEM_DEVICE, stream))
+            _lib.check(lib.pfb_analysis_set_input_quantiser(plan._h, 0, 0.0))
+
+        fns = {"A": side_a, "B": lambda: new_call("B", True, AUTO), "Bs": lambda: new_call("Bs", True, STAGED),
+               "floor": lambda: new_call("floor", False, AUTO)}
+        fns = {k: fns[k] for k in sides}
+        rec = {"kernel": "quantised_input", "shape": "C2 256ch 8/7", "samples": n, "n_pol": n_pol,
+               "in": f"nbit{in_nbit}" if in_nbit else "cf32", "out": f"quantised nbit{out_nbit}" if out_nbit else "cf32",
+               "rms": rms, "calls_per_window": reps, "windows": rounds}
+        # the scales and the outputs, once
+        sa, sb = c_double(0), c_double(0)
+        if "A" in sides:
+            side_a(byref(sa))
+            rec["A_scale"] = sa.value
+        for key in ("B", "Bs"):
+            if key in sides:
+                fns[key]()
+                # (the setter that switched the quantiser off again touches no device state)
+                _lib.check(lib.pfb_analysis_last_input_scale(plan._h, byref(sb), stream))
+                rec[f"{key}_scale"] = sb.value
+                rec[f"{key}_path"] = plan.last_input_quantiser()
+        for k in sides:
+            fns[k]()
+        torch.cuda.synchronize()
+        if "A" in sides and "B" in sides:
+            rec["A_B_float32_scale_bits_equal"] = bool(np.float32(rec["A_scale"]).tobytes() ==
+                                                       np.float32(rec["B_scale"]).tobytes())
+            rec["A_B_outputs_equal"] = bool(torch.equal(out["A"], out["B"]))
+        if "B" in sides and "Bs" in sides:
+            rec["B_Bs_outputs_equal"] = bool(torch.equal(out["B"], out["Bs"]))
+            rec["B_Bs_scale_bits_equal"] = bool(rec["B_scale"] == rec["Bs_scale"])
+        for _ in range(2):
+            for k in sides:
+                timeit(torch, fns[k], reps)
+        t = {k: [] for k in sides}
+        for _ in range(rounds):
+            for k in sides:
+                t[k].append(timeit(torch, fns[k], reps))
+        for k in sides:
+            rec[f"{k}_ms"] = {"median": round(float(np.median(t[k])), 4), "min": round(float(min(t[k])), 4),
+                              "max": round(float(max(t[k])), 4), "spread": round(float(max(t[k]) - min(t[k])), 4)}
+
+        def wins(x, y):  # x's median below y's by more than the larger spread
+            return bool(rec[f"{y}_ms"]["median"] - rec[f"{x}_ms"]["median"] >
+                        max(rec[f"{x}_ms"]["spread"], rec[f"{y}_ms"]["spread"]))
+        for x, y in (("B", "A"), ("B", "Bs"), ("Bs", "B"), ("Bs", "A")):
+            if x in sides and y in sides:
+                rec[f"{x}_below_{y}_by_more_than_spread"] = wins(x, y)
+        # bytes per input sample on top of the analysis's own stores (DESIGN.md §4.12), and the stores
+        per = {"A": 44 if in_nbit else 32, "B": 8 if in_nbit else 16, "Bs": 24 if in_nbit else 32,
+               "floor": 4 if in_nbit else 8}
+        stores = K * C * 8 if not out_nbit else K * C * (8 + 8 + 2 * out_nbit // 8)
+        for k in sides:
+            extra = 4 * K * C * 8 if (out_nbit and k == "A") else 0   # (pfb_quantize's two more passes over the product)
+            rec[f"{k}_bytes"] = int(n_pol * (n * per[k] + stores + extra))
+        print(json.dumps(rec), flush=True)
+        del plan, src, unp, qbuf, cf, out
+        torch.cuda.empty_cache()
 
 
 def dada_synthesis_output(torch, pfb, dev, reps, rounds):

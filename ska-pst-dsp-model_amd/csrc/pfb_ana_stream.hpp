@@ -198,10 +198,17 @@ struct SinkStore {
 // section and the 2-row runs: ZOUT 2, IN a DADA class, OutDada32)
 // MOM: the plain cf32 product with its moments (MomentRowStore): the workgroup's three sums go
 // to a.mom[(pol nw + w) 3 ...] with ordinary stores, zeros from a workgroup without steps
+// QIN: the input quantiser at the load (FilterBank.m:75-83; pfb_analysis_set_input_quantiser,
+// FUSED): every new sample enters the FIR as roundf(sf * IN::cvt(raw)) per component, sf =
+// (float)a.qin[3] (the plan's block, one scalar load; 1 without a block) — the first window and
+// the rows converted when the window slides; the prefetch registers keep the file values, the
+// carried samples (`pre`) are added as they are, a load outside the descriptor gives
+// roundf(sf * 0) = 0, and the carry copy writes the rounded values
 template <int N, int P, int NU, int DE, int ZOUT, bool LCBF, int GS, int TV = 0, class IN = InCf32,
-          class OUT = OutCf32, bool MOM = false>
+          class OUT = OutCf32, bool MOM = false, bool QIN = false>
 __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int pol, int w, int nw) {
   static_assert(!MOM || (!OUT::kDada && ZOUT == 0 && GS == 0 && TV == 0), "moments: the plain cf32 product");
+  static_assert(!QIN || (!OUT::kDada && ZOUT == 0 && GS == 0 && TV == 0), "input quantiser: the plain cf32 product");
   static_assert(!OUT::kDada || (GS == 0 && TV == 0 &&
                                 (ZOUT == 0 || (ZOUT == 2 && !LCBF && IN::kDada && std::is_same<OUT, OutDada32>::value))),
                 "the DADA store: the plain product, or the round trip's float section with 2-row runs");
@@ -210,6 +217,16 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
   constexpr bool kWR = (TV & 8) == 0 && wave_rows_ok<N, T, NT>();
   extern __shared__ __attribute__((aligned(16))) float2 smem[];
   const int c = threadIdx.x;
+  [[maybe_unused]] float sf = 1.f;
+  if constexpr (QIN) {
+    if (a.qin) sf = (float)a.qin[3];
+  }
+  // a sample as it enters the FIR
+  auto cvt = [&](typename IN::raw_t raw) {
+    const v2f v = IN::cvt(raw);
+    if constexpr (QIN) return v2f{roundf(sf * v.x), roundf(sf * v.y)};
+    else return v;
+  };
   if constexpr (ZOUT == 0 && !LCBF) {  // (stream objects only: no round-trip / LowCBF kernel)
   if (a.carry_out) {
     // the next call's carry, grid-stride over this polarisation's workgroups (its few
@@ -224,7 +241,7 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
       for (int64_t i0 = (int64_t)w * NT; i0 < a.carry_n; i0 += (int64_t)nw * NT) {
         const int64_t i = i0 + c;
         if (i < a.carry_n) {
-          const v2f v = IN::cvt(IN::gload(src + i * step));
+          const v2f v = cvt(IN::gload(src + i * step));
           dst[i] = make_float2(v.x, v.y);
         }
       }
@@ -232,7 +249,11 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
     const float2* src = a.in + pol * a.in_pol_stride + a.carry_src;
     for (int64_t i0 = (int64_t)w * NT; i0 < a.carry_n; i0 += (int64_t)nw * NT) {
       const int64_t i = i0 + c;
+      if constexpr (QIN) {
+        if (i < a.carry_n) dst[i] = make_float2(roundf(sf * src[i].x), roundf(sf * src[i].y));
+      } else {
       if (i < a.carry_n) dst[i] = src[i];
+      }
     }
     }
   }
@@ -296,11 +317,11 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
 #pragma unroll
     for (int i = 0; i < WIN; ++i) {
       const v2u pv = __builtin_amdgcn_raw_buffer_load_b64(pr, (uint32_t)(((row_first + i) * N + c) * 8), 0, 0);
-      win[i] = IN::cvt(ld(i)) + __builtin_bit_cast(v2f, pv);
+      win[i] = cvt(ld(i)) + __builtin_bit_cast(v2f, pv);
     }
   } else {
 #pragma unroll
-    for (int i = 0; i < WIN; ++i) win[i] = IN::cvt(ld(i));
+    for (int i = 0; i < WIN; ++i) win[i] = cvt(ld(i));
   }
 
   // LDS: twiddles behind the FFT rows, then F = [N zeros, taps, zeros]
@@ -453,7 +474,7 @@ __device__ __forceinline__ void analysis_stream_body(const AnalysisArgs& a, int 
 #pragma unroll
     for (int i = 0; i < PE - 1; ++i) win[i] = win[i + NEW];
 #pragma unroll
-    for (int i = 0; i < NEW; ++i) win[PE - 1 + i] = IN::cvt(pf[i]);
+    for (int i = 0; i < NEW; ++i) win[PE - 1 + i] = cvt(pf[i]);
     }
   }
   if constexpr (MOM) {
@@ -527,6 +548,48 @@ template <int N, int P, int NU, int DE, bool LCBF, class IN>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void analysis_stream_moments_kernel(AnalysisArgs a) {
   const int w = a.linear ? (int)blockIdx.x : xcd_tile(blockIdx.x, gridDim.x);
   analysis_stream_body<N, P, NU, DE, 0, LCBF, 0, 0, IN, OutCf32, true>(a, blockIdx.y, w, gridDim.x);
+}
+
+// The same kernel with the input quantiser at the load (QIN; AnalysisArgs::qin): the plain cf32
+// product, and the product with its moments.  Kernels of their own names again
+// (pfb_ana_stream_qin.hip instantiates them).
+template <int N, int P, int NU, int DE, bool LCBF, class IN>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void analysis_stream_qin_kernel(AnalysisArgs a) {
+  const int w = a.linear ? (int)blockIdx.x : xcd_tile(blockIdx.x, gridDim.x);
+  analysis_stream_body<N, P, NU, DE, 0, LCBF, 0, 0, IN, OutCf32, false, true>(a, blockIdx.y, w, gridDim.x);
+}
+template <int N, int P, int NU, int DE, bool LCBF, class IN>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void analysis_stream_qin_moments_kernel(AnalysisArgs a) {
+  const int w = a.linear ? (int)blockIdx.x : xcd_tile(blockIdx.x, gridDim.x);
+  analysis_stream_body<N, P, NU, DE, 0, LCBF, 0, 0, IN, OutCf32, true, true>(a, blockIdx.y, w, gridDim.x);
+}
+
+// The one-shot passes beside the streaming kernel (pfb_ana_stream_quant.hip, pfb_ana_stream_qin.hip):
+// their workgroup size, and the 16-byte loads a thread of a moments pass has in flight
+constexpr int kOneShotThreads = 256;
+constexpr int kMomLoads = 8;
+
+// the workgroup's three sums in a fixed order (wave shuffles, then the waves' values through
+// LDS); the result in thread 0
+__device__ __forceinline__ void wg_sum3(double (&m)[3], double* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    m[0] += __shfl_down(m[0], off, 64);
+    m[1] += __shfl_down(m[1], off, 64);
+    m[2] += __shfl_down(m[2], off, 64);
+  }
+  static_assert(kOneShotThreads == 256, "four waves");
+  const int t = threadIdx.x;
+  if ((t & 63) == 0) {
+    red[(t >> 6) * 3 + 0] = m[0];
+    red[(t >> 6) * 3 + 1] = m[1];
+    red[(t >> 6) * 3 + 2] = m[2];
+  }
+  __syncthreads();
+  if (t == 0) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) m[j] = (red[j] + red[3 + j]) + (red[6 + j] + red[9 + j]);
+  }
 }
 
 // Workgroups per polarisation of a streaming launch, each a contiguous range of steps

@@ -13,7 +13,7 @@ namespace pfb {
 
 namespace {
 
-constexpr int QT = 256;  // threads of the one-shot kernels
+constexpr int QT = kOneShotThreads;
 
 template <int N, int P, int NU, int DE, bool LCBF>
 void (*moments_kernel_of(const AnalysisArgs& a))(AnalysisArgs) {
@@ -65,33 +65,11 @@ hipError_t moments_any(const AnalysisArgs& a, bool lcbf, hipStream_t s, int64_t*
   return hipErrorInvalidValue;
 }
 
-// the workgroup's three sums in a fixed order (wave shuffles, then the waves' values through
-// LDS); the result in thread 0
-__device__ __forceinline__ void wg_sum3(double (&m)[3], double* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    m[0] += __shfl_down(m[0], off, 64);
-    m[1] += __shfl_down(m[1], off, 64);
-    m[2] += __shfl_down(m[2], off, 64);
-  }
-  const int t = threadIdx.x;
-  if ((t & 63) == 0) {
-    red[(t >> 6) * 3 + 0] = m[0];
-    red[(t >> 6) * 3 + 1] = m[1];
-    red[(t >> 6) * 3 + 2] = m[2];
-  }
-  __syncthreads();
-  if (t == 0) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) m[j] = (red[j] + red[3 + j]) + (red[6 + j] + red[9 + j]);
-  }
-}
-
 // The moments of a stored product x[pol][0, n) (the STAGED side): workgroup w of polarisation p
 // sums the kMomV x QT 16-byte pairs from pair w kMomV QT on and stores its three doubles at
 // mom[(p nw + w) 3 ...] — the streaming kernel's slot layout.  One-shot grid; n and the pol
 // stride are even and x is 16-B aligned (the launcher checks).
-constexpr int kMomV = 8;
+constexpr int kMomV = kMomLoads;
 __global__ void __launch_bounds__(QT) moments_partials_kernel(const float2* __restrict__ x, int64_t ps, int64_t n,
                                                               double* __restrict__ mom) {
   __shared__ double red[12];

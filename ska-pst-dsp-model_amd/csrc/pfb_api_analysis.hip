@@ -155,10 +155,12 @@ pfb_status pfb::host::analysis_run(pfb_analysis_plan* p, const AnaLaunch& l, hip
   }
   const double in_b = dd ? 2.0 * (dd->nbit / 8) : 8.0;  // bytes per input sample
   const double out_b = od ? 2.0 * (od->nbit / 8) : 8.0;  // bytes per output sample
-  if (l.moments) {
-    // the streaming kernel's moments instantiation: the plain product of all the call's rows
+  if (l.moments || l.qin) {
+    // the streaming kernel's moments instantiation, its input-quantiser instantiation, or both:
+    // the plain product of all the call's rows
     // (a LowCBF plan: its streaming shape, as launch_lowcbf sets it up)
-    if (od || l.z || l.lay || row0 != 0) return fail(PFB_ERR_UNSUPPORTED, "moments: the plain product only");
+    if (od || l.z || l.lay || row0 != 0)
+      return fail(PFB_ERR_UNSUPPORTED, "moments / input quantiser at the load: the plain product only");
     const bool lcbf = p->variant == pfb::kLowCbf;
     pfb::AnalysisArgs a = analysis_args(p, l);
     a.scratch = nullptr;
@@ -170,11 +172,18 @@ pfb_status pfb::host::analysis_run(pfb_analysis_plan* p, const AnaLaunch& l, hip
     }
     const int64_t slots = pfb::stream_moments_slots(a, lcbf);
     if (slots <= 0) return fail(PFB_ERR_UNSUPPORTED, "moments: the plan is not on the streaming kernel");
-    HIPCHK(p->quant_mom.ensure((size_t)slots * 3 * sizeof(double)));
-    a.mom = p->quant_mom.as<double>();
+    if (l.moments) {
+      HIPCHK(p->quant_mom.ensure((size_t)slots * 3 * sizeof(double)));
+      a.mom = p->quant_mom.as<double>();
+    }
     ProfScope ps(0, (double)p->n_pol * (in_b * n_dat + 8.0 * K_end * p->C), s);
-    HIPCHK(pfb::launch_stream_moments(a, lcbf, s));
-    l.moments->slots = slots;
+    if (l.qin) {
+      a.qin = l.qin->stats;
+      HIPCHK(pfb::launch_stream_qin(a, lcbf, s));
+    } else {
+      HIPCHK(pfb::launch_stream_moments(a, lcbf, s));
+    }
+    if (l.moments) l.moments->slots = slots;
     return PFB_OK;
   }
   if (p->variant == pfb::kLowCbf) {
@@ -320,7 +329,7 @@ static void analysis_host_tables(const pfb_analysis_desc* d, const pfb_analysis_
 
 static void analysis_release(pfb_analysis_plan* p) {
   for (DevBuf* b : {&p->taps, &p->twN, &p->zrev, &p->gtab, &p->scratch, &p->carry, &p->carry_next, &p->work, &p->stage_in,
-                    &p->stage_out, &p->dada_stage, &p->quant_prod, &p->quant_mom, &p->quant_stats})
+                    &p->stage_out, &p->dada_stage, &p->quant_prod, &p->quant_mom, &p->quant_stats, &p->qin_mom, &p->qin_stats})
     b->release();
 }
 
@@ -398,6 +407,92 @@ pfb_status pfb::host::section_unpack(const pfb_analysis_plan* p, const DadaSecti
                          s);
 }
 
+// ====================================================================== the input quantiser
+// The input quantiser of one call (pfb_api.h, pfb_analysis_set_input_quantiser).  `on`: the
+// plan's quantiser applies to this call; `fused`: the launch rounds at the load, else the
+// quantising copy (STAGED); stats: the plan's block once qin_moments has enqueued the scale, null
+// for a round-only call (scale 1).
+struct QinCall {
+  bool on = false, fused = false;
+  const double* stats = nullptr;
+};
+
+// the plan is on the streaming kernel (the FUSED side's kernel; section_kernel_shape's LowCBF rule)
+static bool analysis_on_stream_kernel(const pfb_analysis_plan* p) {
+  pfb::AnalysisArgs a;
+  return section_kernel_shape(p, a) && pfb::analysis_writes_dada(a, 32);
+}
+
+// the one-shot passes read such a section where it lies (else it is unpacked first)
+static bool section_readable(const DadaSection& sec) {
+  return sec.ndim == 2 && sec.order == PFB_DADA_TFP && (sec.nbit == 8 || sec.nbit == 16 || sec.nbit == 32) &&
+         reinterpret_cast<uintptr_t>(sec.base) % (size_t)(sec.nbit / 4) == 0;
+}
+
+// The quantiser's own checks for a call of n new samples per polarisation, and its path:
+// fused_ok says whether this call can round at the load.  No launch, no state change.
+static pfb_status qin_check(const pfb_analysis_plan* p, int64_t n, bool fused_ok, QinCall& qc) {
+  qc = QinCall{};
+  if (!p->qin_on) return PFB_OK;
+  if (p->qin_rms > 0 && n > 0 && n * p->n_pol < 2)
+    return fail(PFB_ERR_INVALID_ARG, "input quantiser: the variance needs at least two samples");
+  if (p->qin_mode == PFB_QUANTISER_MOMENTS_FUSED && !fused_ok)
+    return fail(PFB_ERR_UNSUPPORTED, "input quantiser FUSED: this call does not read its new samples in place "
+                                     "on the streaming analysis kernel");
+  qc.on = true;
+  qc.fused = fused_ok && p->qin_mode != PFB_QUANTISER_MOMENTS_STAGED;
+  return PFB_OK;
+}
+
+// The scale of the new samples `src` into the plan's block: the partial sums and the finish
+// launch.  Round only (rms <= 0) and a call without samples take scale 1: nothing is launched.
+static pfb_status qin_moments(pfb_analysis_plan* p, QinCall& qc, const pfb::QinSrc& src, hipStream_t s) {
+  qc.stats = nullptr;
+  p->qin_scale_dev = false;
+  if (p->qin_rms <= 0 || src.n <= 0) return PFB_OK;
+  const int64_t slots = pfb::input_moments_slots(src);
+  HIPCHK(p->qin_mom.ensure((size_t)slots * 3 * sizeof(double)));
+  HIPCHK(p->qin_stats.ensure(4 * sizeof(double)));
+  HIPCHK(pfb::launch_input_moments(src, p->qin_mom.as<double>(), s));
+  HIPCHK(pfb::launch_moments_finish(p->qin_mom.as<double>(), slots, (double)src.n * src.n_pol, p->qin_rms,
+                                    p->qin_stats.as<double>(), s));
+  qc.stats = p->qin_stats.as<double>();
+  p->qin_scale_dev = true;
+  return PFB_OK;
+}
+
+static pfb::QinSrc qin_cf32(const pfb_analysis_plan* p, const float2* x, int64_t ps, int64_t n) {
+  return pfb::QinSrc{x, 0, ps, n, p->n_pol};
+}
+// samples [t0, t0 + n) of a readable section
+static pfb::QinSrc qin_section(const pfb_analysis_plan* p, const DadaSection& sec, int64_t t0, int64_t n) {
+  return pfb::QinSrc{static_cast<const char*>(sec.base) + t0 * p->n_pol * (sec.nbit / 4), sec.nbit, 0, n, p->n_pol};
+}
+
+// STAGED: the new samples, rounded, as packed cf32 at dst[pol][0, n) (pol stride dps) — the
+// moments of the samples where they lie and the quantising copy; a section the passes do not
+// read, or host memory (kind HostToDevice), is unpacked or copied there first and rounded in place
+static pfb_status qin_stage(pfb_analysis_plan* p, QinCall& qc, const float2* in, int64_t in_ps, const DadaSection* sec,
+                            int64_t n, hipMemcpyKind kind, float2* dst, int64_t dps, hipStream_t s) {
+  if (n <= 0) return qin_moments(p, qc, qin_cf32(p, dst, dps, 0), s);
+  pfb::QinSrc src = qin_cf32(p, in, in_ps, n);
+  if (sec && section_readable(*sec)) {
+    src = qin_section(p, *sec, 0, n);
+  } else if (sec || kind != hipMemcpyDeviceToDevice) {
+    if (sec) {
+      const pfb_status st = section_unpack(p, *sec, 0, n, dst, dps, s);
+      if (st != PFB_OK) return st;
+    } else {
+      HIPCHK(copy_pols(dst, dps, in, in_ps, n, p->n_pol, kind, s));
+    }
+    src = qin_cf32(p, dst, dps, n);
+  }
+  const pfb_status st = qin_moments(p, qc, src, s);
+  if (st != PFB_OK) return st;
+  HIPCHK(pfb::launch_quantise_copy(src, qc.stats, dst, dps, s));
+  return PFB_OK;
+}
+
 extern "C" {
 
 // pfb_analysis_execute; sec: the series are a DADA section (device memory) instead of `in`;
@@ -415,10 +510,22 @@ static pfb_status analysis_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_
   const int64_t K = analysis_K(p, n_dat);
   PadConsume pad_once{&p->lowcbf_pad};
   if (n_out) *n_out = K;
+  // the input quantiser: FUSED where the streaming kernel reads the new samples in place and
+  // stores the plain cf32 product (with or without its moments)
+  const bool sec_fus = sec && section_fusable(p, *sec);
+  QinCall qc;
+  {
+    const bool fused_ok = analysis_on_stream_kernel(p) && mem == PFB_MEM_DEVICE && (!sec || sec_fus) && !od;
+    const pfb_status st = qin_check(p, n_dat, fused_ok, qc);
+    if (st != PFB_OK) return st;
+  }
+  const int qin_path = !qc.on ? PFB_INPUT_QUANTISER_NONE : qc.fused ? PFB_INPUT_QUANTISER_FUSED : PFB_INPUT_QUANTISER_STAGED;
   if (K == 0) {
     pad_once.accept();
     // (no launch: the path the section's rows would have taken)
-    if (sec) p->last_dada = section_fusable(p, *sec) ? PFB_DADA_INPUT_FUSED : PFB_DADA_INPUT_STAGED;
+    if (sec) p->last_dada = sec_fus && (!qc.on || qc.fused) ? PFB_DADA_INPUT_FUSED : PFB_DADA_INPUT_STAGED;
+    p->last_qin = qin_path;
+    p->qin_scale_dev = false;
     return PFB_OK;
   }
   if (!out) return fail(PFB_ERR_INVALID_ARG, "null output");
@@ -427,6 +534,7 @@ static pfb_status analysis_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_
   if (mem == PFB_MEM_DEVICE && ((!sec && in_ps < n_dat) || out_ps < K * p->C))
     return fail(PFB_ERR_INVALID_ARG, "polarisation stride smaller than the data");
   pad_once.accept();
+  p->last_qin = qin_path;
   // all K rows of the n_dat samples, into the caller's buffer (or the section od)
   AnaLaunch l;
   l.n_dat = n_dat;
@@ -435,9 +543,29 @@ static pfb_status analysis_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_
   l.K_end = l.K_total = K;
   l.dada_out = od;
   l.moments = mo;
+  AnaQin aq;
+  if (qc.on && !qc.fused && mem == PFB_MEM_DEVICE) {
+    // STAGED: the rounded samples into stage_in, then the plan's cf32 path on them
+    HIPCHK(p->stage_in.ensure((size_t)p->n_pol * n_dat * sizeof(float2)));
+    if (sec) p->last_dada = PFB_DADA_INPUT_STAGED;
+    const pfb_status st = qin_stage(p, qc, (const float2*)in, in_ps, sec, n_dat, hipMemcpyDeviceToDevice,
+                                    p->stage_in.as<float2>(), n_dat, s);
+    if (st != PFB_OK) return st;
+    l.in = p->stage_in.as<float2>();
+    l.in_ps = n_dat;
+    return analysis_run(p, l, s);
+  }
+  if (qc.fused) {
+    // FUSED: the moments of the samples where they lie; the launch rounds at the load
+    const pfb_status st =
+        qin_moments(p, qc, sec ? qin_section(p, *sec, 0, n_dat) : qin_cf32(p, (const float2*)in, in_ps, n_dat), s);
+    if (st != PFB_OK) return st;
+    aq.stats = qc.stats;
+    l.qin = &aq;
+  }
   if (sec) {
     const AnaDada dd{sec->base, sec->nbit};
-    if (section_fusable(p, *sec)) {
+    if (sec_fus) {
       l.dada_in = &dd;
       return analysis_run(p, l, s);
     }
@@ -457,6 +585,12 @@ static pfb_status analysis_exec(pfb_analysis_plan* p, const pfb_cf32* in, int64_
   // host staging (synchronous)
   HIPCHK(p->stage_in.ensure((size_t)p->n_pol * n_dat * sizeof(float2)));
   HIPCHK(p->stage_out.ensure((size_t)p->n_pol * K * p->C * sizeof(float2)));
+  if (qc.on) {
+    // (STAGED: copied, then rounded in place)
+    const pfb_status st = qin_stage(p, qc, (const float2*)in, in_ps, nullptr, n_dat, hipMemcpyHostToDevice,
+                                    p->stage_in.as<float2>(), n_dat, s);
+    if (st != PFB_OK) return st;
+  } else
   HIPCHK(copy_pols(p->stage_in.as<float2>(), n_dat, (const float2*)in, in_ps, n_dat, p->n_pol,
                    hipMemcpyHostToDevice, s));
   l.in = p->stage_in.as<float2>();
@@ -545,11 +679,15 @@ static size_t fb_carry_bytes(const pfb_analysis_plan* p, int64_t nb) {
 // sps), else (neither) already written there by the launch — and the new count.  `into` is the
 // plan's carry, or carry_next where the launch just enqueued still reads the carry: the two
 // then swap.
+// qf: a FUSED input-quantiser call — the tail is rounded as it is copied or unpacked.
 static pfb_status fb_carry(pfb_analysis_plan* p, pfb_analysis_plan::DevBuf& into, int64_t nb, const DadaSection* sec,
-                           int64_t t0, const float2* src, int64_t sps, hipStream_t s) {
+                           int64_t t0, const float2* src, int64_t sps, hipStream_t s, const QinCall* qf = nullptr) {
   if (nb > 0) {
     HIPCHK(into.ensure(fb_carry_bytes(p, nb)));
-    if (sec) {
+    if (qf && (sec || src)) {
+      HIPCHK(pfb::launch_quantise_copy(sec ? qin_section(p, *sec, t0, nb) : qin_cf32(p, src, sps, nb), qf->stats,
+                                       into.as<float2>(), nb, s));
+    } else if (sec) {
       const pfb_status st = section_unpack(p, *sec, t0, nb, into.as<float2>(), nb, s);
       if (st != PFB_OK) return st;
     } else if (src) {
@@ -579,7 +717,9 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
   hipStream_t s = (hipStream_t)stream;
   // FUSED: the kernel reads the section's new samples in place; STAGED: they are unpacked
   // behind the carry in the concatenation buffer and the cf32 path runs
-  const bool fus = sec && section_fusable(p, *sec);
+  // (not const: a STAGED input-quantiser call that rounds its samples into stage_in goes on as
+  // the cf32 device call on them)
+  bool fus = sec && section_fusable(p, *sec);
   const AnaDada dd_{sec ? sec->base : nullptr, sec ? sec->nbit : 0};
   const AnaDada* dd = fus ? &dd_ : nullptr;
   const int last_dada = !sec ? PFB_DADA_INPUT_NONE : PFB_DADA_INPUT_STAGED;  // (a fused launch sets FUSED)
@@ -602,6 +742,58 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
   l.K_total = K;
   l.dada_out = od;
   l.moments = mo;
+  // The conditions of the two carry paths below, as functions of the input side: (a section, read
+  // in place) — the input quantiser asks them for the call as it is and, STAGED, for the cf32
+  // device call on the rounded samples.
+  // (split: the streaming kernel's register window holds the carry — the bound is explained below)
+  static const bool no_split = pfb::knob("PFB_FB_NO_SPLIT") != nullptr;  // A/B
+  const int64_t win = ((int64_t)p->de * (16 / p->nu) + p->P) * p->N;
+  auto split_ok = [&](bool has_sec, bool sec_fused) {
+    const bool lcbf_sec = has_sec && sec_fused && p->variant == pfb::kLowCbf;
+    return !no_split && mem == PFB_MEM_DEVICE && B > 0 && B <= win &&
+           ((p->variant == pfb::kBunton && analysis_offset_ok(p)) || lcbf_sec) && input_idat >= B &&
+           p->lowcbf_pad == false && (!has_sec || sec_fused);
+  };
+  auto fused_carry_ok = [&](bool has_sec) {
+    return !has_sec && !od && !mo && mem == PFB_MEM_DEVICE && B > 0 && !p->lowcbf_pad && p->fused &&
+           analysis_fused_carry_ok(p) && input_idat >= B && Kt > 0;
+  };
+  // The input quantiser (pfb_api.h).  FUSED: the streaming kernel reads the new samples in place
+  // (the split launch, or nothing buffered) and stores the plain cf32 product.
+  QinCall qc;
+  {
+    const bool in_place_now = B == 0 && mem == PFB_MEM_DEVICE && (!sec || fus);
+    const bool fused_ok = analysis_on_stream_kernel(p) && !od && !lay && (split_ok(sec != nullptr, fus) || in_place_now);
+    const pfb_status st = qin_check(p, n_in, fused_ok, qc);
+    if (st != PFB_OK) return st;
+  }
+  // (a call the capacity check below rejects: nothing is launched for the quantiser either)
+  if (Kt > cap) qc.on = qc.fused = false;
+  if (qc.on || !p->qin_on) p->last_qin = !qc.on ? PFB_INPUT_QUANTISER_NONE : qc.fused ? PFB_INPUT_QUANTISER_FUSED : PFB_INPUT_QUANTISER_STAGED;
+  const QinCall* qfused = qc.fused ? &qc : nullptr;
+  AnaQin aq;
+  // STAGED, when the call on the rounded samples reads them in place (a carry path, or nothing
+  // buffered): rounded into stage_in, and the call goes on as the cf32 device call on them.
+  // (A call that concatenates rounds them into the work buffer, behind the carry: below.)
+  bool qin_staged_in = false;
+  if (qc.on && !qc.fused && mem == PFB_MEM_DEVICE && (B == 0 || split_ok(false, false) || fused_carry_ok(false))) {
+    HIPCHK(p->stage_in.ensure((size_t)p->n_pol * std::max<int64_t>(n_in, 1) * sizeof(float2)));
+    const pfb_status st = qin_stage(p, qc, (const float2*)in, in_ps, sec, n_in, hipMemcpyDeviceToDevice,
+                                    p->stage_in.as<float2>(), std::max<int64_t>(n_in, 1), s);
+    if (st != PFB_OK) return st;
+    in = p->stage_in.as<pfb_cf32>();
+    in_ps = std::max<int64_t>(n_in, 1);
+    sec = nullptr;
+    fus = false;
+    dd = nullptr;
+    qin_staged_in = true;
+  } else if (qc.fused) {
+    const pfb_status st =
+        qin_moments(p, qc, sec ? qin_section(p, *sec, 0, n_in) : qin_cf32(p, (const float2*)in, in_ps, n_in), s);
+    if (st != PFB_OK) return st;
+    aq.stats = qc.stats;
+    l.qin = &aq;
+  }
   {
     // Carry without the concatenation copy (streaming analysis kernel, device input): when
     // the new carry starts in the new input (input_idat >= B), ONE launch reads the new
@@ -609,20 +801,17 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
     // the carried samples themselves through a second descriptor in its first register
     // window (AnalysisArgs::pre).  The result is the same per row as the concatenated run
     // (same kernel, same samples).
-    static const bool no_split = pfb::knob("PFB_FB_NO_SPLIT") != nullptr;  // A/B
-    // the streaming kernel's register window: DE (16 / NU) new rows per step + P (its first
+    // (split_ok, above)
+    // the streaming kernel's register window (win): DE (16 / NU) new rows per step + P (its first
     // window holds every carried sample a workgroup's rows read when B fits in it —
     // launch_stream checks the same bound).  A stream call leaves at most P N + NU M - 1
     // samples behind (total - Kt M with K - Kt < NU), which is below the window's
     // P N + 16 M for every NU <= 16: every carry this object makes fits
     // (tests/test_stream_model.py enumerates it); a longer one would concatenate below.
-    const int64_t win = ((int64_t)p->de * (16 / p->nu) + p->P) * p->N;
     // (a DADA section: fused only, else staged; a fused LowCBF stream call takes this path
     // too — its cf32 call concatenates)
     const bool lcbf_dd = dd && p->variant == pfb::kLowCbf;
-    if (!no_split && mem == PFB_MEM_DEVICE && B > 0 && B <= win &&
-        ((p->variant == pfb::kBunton && analysis_offset_ok(p)) || lcbf_dd) && input_idat >= B &&
-        p->lowcbf_pad == false && (!sec || fus)) {
+    if (split_ok(sec != nullptr, fus)) {
       if (n_out) *n_out = Kt;
       if (Kt > cap) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld rows",
                                 (long long)cap, (long long)Kt);
@@ -652,7 +841,8 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
       l.dada_in = dd;
       const pfb_status st = analysis_run(p, l, s);
       if (st != PFB_OK) return st;
-      return fb_carry(p, p->carry_next, nb, lcbf_dd ? sec : nullptr, input_idat - B, nullptr, 0, s);
+      // (with the input quantiser FUSED: rounded as it is unpacked)
+      return fb_carry(p, p->carry_next, nb, lcbf_dd ? sec : nullptr, input_idat - B, nullptr, 0, s, qfused);
     }
   }
   {
@@ -663,8 +853,7 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
     // (a layout — pfb_filterbank_execute_strided on a padded plan; the Bunton plans it admits
     // take the streaming kernel above — goes straight to `out`: no scratch rows and no staging
     // buffer, fb_rows_dst)
-    if (!sec && !od && !mo && mem == PFB_MEM_DEVICE && B > 0 && !p->lowcbf_pad && p->fused && analysis_fused_carry_ok(p) &&
-        input_idat >= B && Kt > 0) {
+    if (fused_carry_ok(sec != nullptr)) {
       p->last_dada = last_dada;
       if (n_out) *n_out = Kt;
       if (Kt > cap) return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld rows",
@@ -698,7 +887,12 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
     HIPCHK(p->work.ensure((size_t)p->n_pol * std::max<int64_t>(total, 1) * sizeof(float2)));
     float2* wk = p->work.as<float2>();
     HIPCHK(copy_pols(wk, total, p->carry.as<float2>(), B, B, p->n_pol, hipMemcpyDeviceToDevice, s));
-    if (sec) {
+    if (qc.on && !qin_staged_in) {
+      // (the input quantiser, STAGED: the quantising copy stands where the call copies or
+      // unpacks its new samples)
+      const pfb_status st = qin_stage(p, qc, (const float2*)in, in_ps, sec, n_in, kin, wk + B, total, s);
+      if (st != PFB_OK) return st;
+    } else if (sec) {
       // (unpacked straight behind the carry: no second copy)
       const pfb_status st = section_unpack(p, *sec, 0, n_in, wk + B, total, s);
       if (st != PFB_OK) return st;
@@ -732,7 +926,8 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
   }
   // carry = input(:,:,input_idat+1:end)   (FilterBank.m:119-126); a separate buffer, it aliases
   // nothing in `work`.  (a fused section: its tail, unpacked)
-  const pfb_status st = fb_carry(p, p->carry, nb, dd ? sec : nullptr, input_idat, w + input_idat, wps, s);
+  // (the input quantiser FUSED — read in place, nothing buffered: rounded as it is copied)
+  const pfb_status st = fb_carry(p, p->carry, nb, dd ? sec : nullptr, input_idat, w + input_idat, wps, s, qfused);
   if (st != PFB_OK) return st;
   if (mem == PFB_MEM_HOST) HIPCHK(hipStreamSynchronize(s));
   return PFB_OK;
@@ -1023,6 +1218,36 @@ pfb_status pfb_analysis_set_quantiser_moments(pfb_analysis_plan* p, int32_t mode
 }
 
 int32_t pfb_analysis_last_quantiser(const pfb_analysis_plan* p) { return p ? p->last_quant : -1; }
+
+pfb_status pfb_analysis_set_input_quantiser(pfb_analysis_plan* p, int32_t enable, double rms) {
+  if (!p) return fail(PFB_ERR_INVALID_ARG, "null plan");
+  if (!std::isfinite(rms)) return fail(PFB_ERR_INVALID_ARG, "input quantiser rms is not finite");
+  p->qin_on = enable != 0;
+  p->qin_rms = rms;
+  return PFB_OK;
+}
+
+pfb_status pfb_analysis_set_input_quantiser_mode(pfb_analysis_plan* p, int32_t mode) {
+  if (!p) return fail(PFB_ERR_INVALID_ARG, "null plan");
+  if (mode != PFB_QUANTISER_MOMENTS_AUTO && mode != PFB_QUANTISER_MOMENTS_FUSED &&
+      mode != PFB_QUANTISER_MOMENTS_STAGED)
+    return fail(PFB_ERR_INVALID_ARG, "unknown input quantiser mode %d", mode);
+  p->qin_mode = mode;
+  return PFB_OK;
+}
+
+int32_t pfb_analysis_last_input_quantiser(const pfb_analysis_plan* p) { return p ? p->last_qin : -1; }
+
+pfb_status pfb_analysis_last_input_scale(pfb_analysis_plan* p, double* scale, void* stream) {
+  if (!p || !scale) return fail(PFB_ERR_INVALID_ARG, "null argument");
+  *scale = 1.0;
+  if (!p->qin_scale_dev) return PFB_OK;
+  HIPCHK(hipSetDevice(p->device));
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipMemcpyAsync(scale, p->qin_stats.as<double>() + 3, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return PFB_OK;
+}
 
 
 int64_t pfb_filterbank_buffered(const pfb_analysis_plan* p) { return p ? p->buffered : -1; }

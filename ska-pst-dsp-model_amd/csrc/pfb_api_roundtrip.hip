@@ -71,6 +71,8 @@ static pfb_status roundtrip_run(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, c
   if (opt.wave2) *opt.wave2 = false;
   if (!pa || !ps || (!x && n_dat > 0 && phase != 2)) return fail(PFB_ERR_INVALID_ARG, "null argument");
   if (pa->device != ps->device) return fail(PFB_ERR_INVALID_ARG, "plans on different devices");
+  if (pa->qin_on)
+    return fail(PFB_ERR_UNSUPPORTED, "round trip with the input quantiser on: use the separate calls");
   if (pa->variant == pfb::kLowCbf)
     return fail(PFB_ERR_UNSUPPORTED, "round trip of the LowCBF filterbank: use the separate calls");
   if (pa->N != ps->N || pa->n_pol != ps->n_pol)
@@ -408,6 +410,8 @@ static pfb_status roundtrip_dada(pfb_analysis_plan* pa, pfb_synthesis_plan* ps, 
   const int phase = call.phase;
   const int64_t n_dat = call.n_dat;
   if (!pa || !ps) return fail(PFB_ERR_INVALID_ARG, "null plan");
+  if (pa->qin_on)
+    return fail(PFB_ERR_UNSUPPORTED, "round trip with the input quantiser on: use the separate calls");
   if (phase != 2) {
     const pfb_status st = section_check(pa, sec.in, n_dat);
     if (st != PFB_OK) return st;

@@ -184,6 +184,15 @@ struct pfb_analysis_plan {
   DevBuf quant_prod, quant_mom, quant_stats;
   int quant_mode = PFB_QUANTISER_MOMENTS_AUTO;  // pfb_analysis_set_quantiser_moments
   int last_quant = PFB_QUANTISER_NONE;          // pfb_analysis_last_quantiser
+  // the quantised input (pfb_analysis_set_input_quantiser): the partial sums of the new samples'
+  // moments and the 32-byte block of their own (the output quantiser's can be live in the same
+  // call), grown with the call's length
+  DevBuf qin_mom, qin_stats;
+  bool qin_on = false;
+  double qin_rms = 0.0;
+  int qin_mode = PFB_QUANTISER_MOMENTS_AUTO;    // pfb_analysis_set_input_quantiser_mode
+  int last_qin = PFB_INPUT_QUANTISER_NONE;      // pfb_analysis_last_input_quantiser
+  bool qin_scale_dev = false;  // the last call's scale is qin_stats[3] (else 1: pfb_analysis_last_input_scale)
   // round trip (pfb_roundtrip_execute): the analysis runs on this stream, ahead of the
   // synthesis on the caller's stream; one event per chunk orders them
   hipStream_t aux = nullptr;
@@ -289,6 +298,12 @@ struct AnaMoments {
   int64_t slots = 0;
 };
 
+// The launch replaces every new sample x by roundf(sf * x) as it loads it, sf = (float)stats[3]
+// of the plan's input-quantiser block, 1 when stats is null (AnalysisArgs::qin)
+struct AnaQin {
+  const double* stats = nullptr;
+};
+
 // One analysis launch (analysis_run); a call site sets the members it uses.
 struct AnaLaunch {
   // input: n_dat samples per pol from `in`, which starts `pad` samples into the series (a read
@@ -318,6 +333,9 @@ struct AnaLaunch {
   const AnaOut* dada_out = nullptr;
   // the launch stores the plain cf32 product and its moments (streaming-kernel plans only)
   AnaMoments* moments = nullptr;
+  // the launch rounds its new samples at the load (the input quantiser, FUSED: streaming-kernel
+  // plans, the plain cf32 product with or without its moments)
+  const AnaQin* qin = nullptr;
 };
 
 pfb_status analysis_run(pfb_analysis_plan* p, const AnaLaunch& l, hipStream_t s);

@@ -122,6 +122,11 @@ struct AnalysisArgs {
   // w of polarisation p of a grid of nw per polarisation stores (sum re, sum im, sum re^2 + im^2)
   // of the values it stored, in double, at mom[(p nw + w) 3 ...]
   double* mom = nullptr;
+  // The input quantiser at the load (analysis_stream_qin_kernel, launch_stream_qin): every new
+  // sample enters the FIR as roundf(sf * x) per component, sf = (float)qin[3] of the plan's
+  // block {sum re, sum im, s2, scale} (launch_moments_finish), 1 when null.  Read only by the
+  // QIN instantiations.
+  const double* qin = nullptr;
 };
 // the plan's kernel has a loader for such a section (the streaming kernel; the LDS-shared FIR
 // of the N > 256 path, launches without stage-1 rows)
@@ -152,6 +157,30 @@ hipError_t launch_moments_finish(const double* mom, int64_t slots, double cnt, d
 // each component to_sample(out_scale * roundf(sf * x)), sf = (float)stats[3] or 1 (stats null)
 hipError_t launch_quantise_pack(const float2* x, int64_t ps, int64_t n, int n_pol, const double* stats,
                                 float out_scale, void* out, int nbit, hipStream_t s);
+// The quantised input (pfb_ana_stream_qin.hip; pfb_analysis_set_input_quantiser).
+// The new samples of a call, read where they lie: cf32 rows x[pol][0, n) (pol stride ps), or a
+// single-channel TFP section (NDIM 2, nbit 8 / 16 / 32, aligned to one complex sample; nbit 0:
+// cf32) of n samples x n_pol polarisations from its sample 0.
+struct QinSrc {
+  const void* base;
+  int nbit;      // 0: cf32 rows
+  int64_t ps;    // cf32: pol stride in samples
+  int64_t n;     // samples per polarisation
+  int n_pol;
+};
+// Their moments in the slot layout launch_moments_finish adds: one slot of three doubles per
+// workgroup of a one-shot grid, ordinary stores, 16-byte loads of the aligned middle of each
+// row (a section is one row of n n_pol samples) and single samples at its ragged ends; no byte
+// outside the rows is read.  input_moments_slots: their number (0: no samples).
+int64_t input_moments_slots(const QinSrc& q);
+hipError_t launch_input_moments(const QinSrc& q, double* mom, hipStream_t s);
+// dst[pol][0, n) (pol stride dps, packed cf32) = roundf(sf * x) per component, sf = (float)stats[3]
+// or 1 (stats null): the quantising copy of the STAGED side and of the carry tail; dst may be
+// the cf32 source itself (element for element)
+hipError_t launch_quantise_copy(const QinSrc& q, const double* stats, float2* dst, int64_t dps, hipStream_t s);
+// The streaming kernel rounding at the load (AnalysisArgs::qin; the plain cf32 product, or with
+// a.mom the product's moments as launch_stream_moments); lcbf: the LowCBF instantiation
+hipError_t launch_stream_qin(const AnalysisArgs& a, bool lcbf, hipStream_t s);
 // The file-to-file round trip's analysis launch (pfb_ana_stream_rtdada.hip): the streaming
 // kernel reading the section `din` (in_nbit 8 / 16 / 32) in place, storing the product as the
 // NBIT 32 float section `dout` (dout_scale 1) and the stage-1 rows z in 2-row runs (zblk 2) —

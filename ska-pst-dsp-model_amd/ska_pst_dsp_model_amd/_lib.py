@@ -53,6 +53,9 @@ PFB_QUANTISER_MOMENTS_STAGED = 2
 PFB_QUANTISER_NONE = 0
 PFB_QUANTISER_FUSED = 1
 PFB_QUANTISER_STAGED = 2
+PFB_INPUT_QUANTISER_NONE = 0
+PFB_INPUT_QUANTISER_FUSED = 1
+PFB_INPUT_QUANTISER_STAGED = 2
 PFB_STRIDED_INPUT_NONE = 0
 PFB_STRIDED_INPUT_IN_PLACE = 1
 PFB_STRIDED_INPUT_STAGED = 2
@@ -168,6 +171,10 @@ SYMBOLS = [
                                                                 c_void_p]),
     ("pfb_analysis_set_quantiser_moments", c_int32, [c_void_p, c_int32]),
     ("pfb_analysis_last_quantiser", c_int32, [c_void_p]),
+    ("pfb_analysis_set_input_quantiser", c_int32, [c_void_p, c_int32, c_double]),
+    ("pfb_analysis_set_input_quantiser_mode", c_int32, [c_void_p, c_int32]),
+    ("pfb_analysis_last_input_quantiser", c_int32, [c_void_p]),
+    ("pfb_analysis_last_input_scale", c_int32, [c_void_p, POINTER(c_double), c_void_p]),
     ("pfb_synthesis_execute_to_dada", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                                 c_int32, c_float, c_int64, POINTER(c_int64), c_void_p]),
     ("pfb_inverse_filterbank_execute_to_dada", c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p,

@@ -130,6 +130,7 @@ def _order(lowcbf: bool) -> int:
 _DADA_INPUT_NAMES = {_lib.PFB_DADA_INPUT_FUSED: "fused", _lib.PFB_DADA_INPUT_STAGED: "staged"}
 _DADA_OUTPUT_NAMES = {_lib.PFB_DADA_OUTPUT_FUSED: "fused", _lib.PFB_DADA_OUTPUT_STAGED: "staged"}
 _QUANTISER_NAMES = {_lib.PFB_QUANTISER_FUSED: "fused", _lib.PFB_QUANTISER_STAGED: "staged"}
+_INPUT_QUANTISER_NAMES = {_lib.PFB_INPUT_QUANTISER_FUSED: "fused", _lib.PFB_INPUT_QUANTISER_STAGED: "staged"}
 _STRIDED_INPUT_NAMES = {_lib.PFB_STRIDED_INPUT_IN_PLACE: "in_place",
                         _lib.PFB_STRIDED_INPUT_STAGED: "staged"}
 _STAGE1_NAMES = {_lib.PFB_STAGE1_STORED: "stored", _lib.PFB_STAGE1_RECOMPUTED: "recomputed"}
@@ -445,6 +446,41 @@ class AnalysisPlan(_Plan):
         """The path of the plan's last quantised to-DADA call: 'fused', 'staged', or 'none' (no
         such call, or another execute call since) — pfb_analysis_last_quantiser."""
         return _mode_name(self, "pfb_analysis_last_quantiser", _QUANTISER_NAMES)
+
+    def set_input_quantiser(self, rms):
+        """The FilterBank's input quantiser (FilterBank.m:75-83) as a property of the plan: with
+        ``rms`` a number, every execute call replaces its own new samples by
+        ``round(float32(s) * x)``, ``s = rms / std(x)`` over the call's new samples of every
+        polarisation (``rms <= 0``: round only), before the carried samples are put in front;
+        ``None`` turns it off (the default) — pfb_analysis_set_input_quantiser.  Takes effect at
+        the next call; may be set with samples buffered."""
+        on = rms is not None
+        _lib.check(self._lib.pfb_analysis_set_input_quantiser(self._h, int(on), float(rms) if on else 0.0))
+
+    def set_input_quantiser_mode(self, mode: str):
+        """Where the input quantiser rounds: 'auto' (at the analysis kernel's load where the call
+        reads its new samples in place on the streaming kernel), 'fused' (there or
+        PFB_ERR_UNSUPPORTED), 'staged' (always a quantising copy first) —
+        pfb_analysis_set_input_quantiser_mode."""
+        modes = {"auto": _lib.PFB_QUANTISER_MOMENTS_AUTO, "fused": _lib.PFB_QUANTISER_MOMENTS_FUSED,
+                 "staged": _lib.PFB_QUANTISER_MOMENTS_STAGED}
+        if mode not in modes:
+            raise ValueError(f"input quantiser mode {mode!r}: one of {sorted(modes)}")
+        _lib.check(self._lib.pfb_analysis_set_input_quantiser_mode(self._h, modes[mode]))
+
+    def last_input_quantiser(self) -> str:
+        """The input quantiser's path in the plan's last call: 'fused', 'staged', or 'none' (off,
+        or no call yet) — pfb_analysis_last_input_quantiser."""
+        return _mode_name(self, "pfb_analysis_last_input_quantiser", _INPUT_QUANTISER_NAMES)
+
+    def last_input_scale(self) -> float:
+        """The scale the input quantiser took in the plan's last call (1 for a round-only call or
+        one without samples); waits for the device — pfb_analysis_last_input_scale."""
+        t = _torch()
+        got = c_double(1.0)
+        stream = c_void_p(t.cuda.current_stream(t.device("cuda", self.device)).cuda_stream)
+        _lib.check(self._lib.pfb_analysis_last_input_scale(self._h, byref(got), stream))
+        return float(got.value)
 
 
 # ============================================================================ synthesis

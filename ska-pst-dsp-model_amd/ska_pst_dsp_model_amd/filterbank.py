@@ -74,7 +74,8 @@ def _quantize(x, rms, device=0):
 class FilterBank(Channelizer):
     """FilterBank.m:1-130 — analysis PFB with input buffering and nu-trimming."""
 
-    def __init__(self, config=None, n_pol: int = None, device: int = 0, fused_quantiser: bool = None):
+    def __init__(self, config=None, n_pol: int = None, device: int = 0, fused_quantiser: bool = None,
+                 fused_input_quantiser: bool = None):
         self.pfb_analysis = "polyphase_analysis"
         self.os_factor = None
         self.filt_coeff = None
@@ -86,6 +87,10 @@ class FilterBank(Channelizer):
         # opt-in: the to-DADA calls take the output quantiser through the plan's quantised
         # calls (AnalysisPlan.execute_quantised_to_dada) instead of the execute fallback
         self.fused_quantiser = False
+        # opt-in: ``rndInput`` is taken by the plan's input quantiser
+        # (AnalysisPlan.set_input_quantiser, rms = rmsInput) on every execute entry, instead of
+        # pfb_quantize into a fresh buffer and the fallbacks that follow from it
+        self.fused_input_quantiser = False
         self.device = device
         self._plan = None
         self._n_pol = n_pol
@@ -99,13 +104,25 @@ class FilterBank(Channelizer):
             self.rndOutput = bool(_cfg(config, "rndOutput", False))
             self.rmsOutput = float(_cfg(config, "rmsOutput", 0.0))
             self.fused_quantiser = bool(_cfg(config, "fused_quantiser", False))
+            self.fused_input_quantiser = bool(_cfg(config, "fused_input_quantiser", False))
         if fused_quantiser is not None:
             self.fused_quantiser = bool(fused_quantiser)
+        if fused_input_quantiser is not None:
+            self.fused_input_quantiser = bool(fused_input_quantiser)
+
+    def _input_fused(self) -> bool:
+        """``rndInput`` goes through the plan's input quantiser: opted in and configured."""
+        return bool(self.fused_input_quantiser and self.rndInput)
+
+    def _input_fallback(self) -> bool:
+        """``rndInput`` is configured and takes ``_quantize`` on the input (no opt-in)."""
+        return bool(self.rndInput and not self._input_fused())
 
     def _quantiser_fused(self) -> bool:
         """The to-DADA calls take the plan's quantised calls: opted in, the output quantiser
-        configured and no input quantiser (whose scale needs the whole input first)."""
-        return bool(self.fused_quantiser and self.rndOutput and not self.rndInput)
+        configured and no input quantiser outside the plan (whose scale needs the whole input
+        first; with ``fused_input_quantiser`` the plan takes it in the same call)."""
+        return bool(self.fused_quantiser and self.rndOutput and not self._input_fallback())
 
     def _ensure_plan(self, n_pol):
         if self._plan is None or self._plan.n_pol != n_pol:
@@ -113,6 +130,8 @@ class FilterBank(Channelizer):
                 raise ValueError("n_pol changed while samples are buffered")
             self._plan = AnalysisPlan(self.filt_coeff, self.n_chan, self.os_factor,
                                       self.pfb_analysis, n_pol, self.device)
+        # (host-side state of the plan: takes effect at the next call)
+        self._plan.set_input_quantiser(self.rmsInput if self._input_fused() else None)
         return self._plan
 
     @property
@@ -121,7 +140,7 @@ class FilterBank(Channelizer):
 
     def execute(self, input):  # noqa: A002
         x = input
-        if self.rndInput:
+        if self._input_fallback():
             x = _quantize(x, self.rmsInput, self.device)
         plan = self._ensure_plan(_npol(x))
         out = plan.execute(x, stateful=True)  # (n_pol, T_out, n_chan)
@@ -135,8 +154,10 @@ class FilterBank(Channelizer):
         polarisations interleaved (TFP).  Same output and carry as
         ``execute(DADARead.generate(...)[:, 0, :])``, bit for bit
         (``AnalysisPlan.execute_dada``).  With ``rndInput`` set the section is unpacked and
-        takes ``execute``: the quantiser's scale needs the variance of the whole input."""
-        if self.rndInput:
+        takes ``execute``: the quantiser's scale needs the variance of the whole input — unless
+        ``fused_input_quantiser`` is set: the plan's input quantiser then takes the moments of
+        the section where it lies and the kernel rounds as it loads."""
+        if self._input_fallback():
             x = layout.dada_unpack(raw, nbit, ndim, 1, int(n_pol))[:, :, 0]
             return self.execute(x)
         plan = self._ensure_plan(int(n_pol))
@@ -156,11 +177,12 @@ class FilterBank(Channelizer):
         ``execute`` followed by ``layout.dada_pack`` — unless ``fused_quantiser`` is set, which
         sends the ``rndOutput`` case (without ``rndInput``) through
         ``AnalysisPlan.execute_quantised_to_dada`` with ``rms = rmsOutput``: the moments summed
-        by the analysis kernel, one pass over the product."""
+        by the analysis kernel, one pass over the product.  With ``fused_input_quantiser``
+        ``rndInput`` is the plan's input quantiser and causes no fallback."""
         if self._quantiser_fused():
             plan = self._ensure_plan(_npol(input))
             return self, plan.execute_quantised_to_dada(input, nbit, self.rmsOutput, scale=scale, stateful=True)
-        if self.rndInput or self.rndOutput or self.rmsOutput:
+        if self._input_fallback() or self.rndOutput or self.rmsOutput:
             _, view = self.execute(input)
             return self, self._pack_view(view, nbit, scale)
         plan = self._ensure_plan(_npol(input))
@@ -175,7 +197,7 @@ class FilterBank(Channelizer):
             plan = self._ensure_plan(int(n_pol))
             return self, plan.execute_dada_quantised_to_dada(raw, in_nbit, out_nbit, self.rmsOutput, scale=scale,
                                                              ndim=ndim, stateful=True)
-        if self.rndInput or self.rndOutput or self.rmsOutput:
+        if self._input_fallback() or self.rndOutput or self.rmsOutput:
             _, view = self.execute_dada(raw, in_nbit, ndim=ndim, n_pol=n_pol)
             return self, self._pack_view(view, out_nbit, scale)
         plan = self._ensure_plan(int(n_pol))
@@ -357,7 +379,9 @@ class TwoStageFilterBank(Channelizer):
     _STRIDED_DEFAULT = {"padded": (True, True), "other": (True, True)}
 
     def __init__(self, config, device: int = 0):
-        self.stage1 = FilterBank(config, device=device)
+        # (the stages' input quantiser stays pfb_quantize: the batched stage-2 plan's variance
+        # would run over all its series at once)
+        self.stage1 = FilterBank(config, device=device, fused_input_quantiser=False)
         self.config1 = config
         self.config2 = config
         self.nch1 = int(_cfg(config, "channels"))
@@ -380,7 +404,7 @@ class TwoStageFilterBank(Channelizer):
         return self
 
     def build(self):
-        self.stage2 = FilterBank(self.config2, device=self.device)
+        self.stage2 = FilterBank(self.config2, device=self.device, fused_input_quantiser=False)
         self.built = True
         return self
 
