@@ -469,8 +469,18 @@ int32_t pfb_analysis_last_dada_input(const pfb_analysis_plan* plan);
  * nbit equals out_nbit or out_nbit is 32 (an integer file channelised into a float one); any
  * other input section is unpacked into the plan's staging buffer first and the output stays
  * fused (pfb_analysis_last_dada_input then reports STAGED).
- * STAGED: every other plan (the padded variant with its circular row shift, n_chan other than
- * 256, the FIR + row-FFT path), out_nbit 64 and an `out` aligned to a value but not to a
+ * FUSED as well, under the same conditions on out_nbit and `out`: every plan with n_chan 4096
+ * (PFB_ANALYSIS_BUNTON and PFB_ANALYSIS_PADDED; stateless and stream calls).  Their FIR fills the
+ * plan's scratch rows as ever and the 4096-point row FFT converts and stores the section itself,
+ * one descriptor per row of the section, 4096 * P * (out_nbit / 4) <= 0x7ffffff0, which holds
+ * for every plan; with two polarisations one workgroup stores both, 4 / 8 / 16 bytes per bin.  A
+ * padded stream call computes the rows its circular shift spans and makes only the *n_out kept
+ * ones; no buffer holds the others.  FIR and row FFT are launches of their own, so the
+ * _dada_to_dada calls read the input section exactly as pfb_analysis_execute_dada does on the
+ * same plan and state, whatever the two NBITs.
+ * STAGED: every other plan (the padded variant with its circular row shift and the FIR +
+ * row-FFT path at n_chan other than 4096, the other n_chan of the Bunton variant), out_nbit 64
+ * and an `out` aligned to a value but not to a
  * complex sample run the cf32 path into a plan-owned buffer, then one scaled pack launch; so
  * these calls accept every plan the cf32 calls accept.
  * pfb_analysis_last_dada_output: which of the two the plan's last such call took, NONE before

@@ -78,6 +78,9 @@ def main():
                     help="the dada_analysis A/B alone (--reps: calls per timed window)")
     ap.add_argument("--only-dada-output", action="store_true",
                     help="the dada_output A/B alone (--reps: calls per timed window)")
+    ap.add_argument("--parent-lib", default=None,
+                    help="with --only-dada-output: a libpfb_hip.so built from the parent commit; its to-DADA "
+                         "call is timed as a third side P of the SKA-Mid rows")
     ap.add_argument("--only-dada-synthesis-output", action="store_true",
                     help="the dada_synthesis_output A/B alone (--reps: calls per timed window)")
     ap.add_argument("--only-dada-roundtrip", action="store_true",
@@ -128,7 +131,7 @@ def main():
     if args.only_dada_analysis:
         return dada_analysis(torch, pfb, dev, max(args.reps, 20), args.rounds)
     if args.only_dada_output:
-        return dada_output(torch, pfb, dev, max(args.reps, 20), args.rounds)
+        return dada_output(torch, pfb, dev, max(args.reps, 20), args.rounds, args.parent_lib)
     if args.only_dada_synthesis_output:
         return dada_synthesis_output(torch, pfb, dev, max(args.reps, 20), args.rounds)
     if args.only_dada_roundtrip:
@@ -383,7 +386,7 @@ def dada_analysis(torch, pfb, dev, reps, rounds):
         torch.cuda.empty_cache()
 
 
-def dada_output(torch, pfb, dev, reps, rounds):
+def dada_output(torch, pfb, dev, reps, rounds, parent_lib=None):
     """Channelised product -> DADA section (TFP, NBIT 8 / 16 / 32).  A: the pair a caller had
     before — the cf32-output call (pfb_analysis_execute, or pfb_analysis_execute_dada for a
     DADA input), both components times the scale in float32 (one elementwise pass), then
@@ -392,10 +395,16 @@ def dada_output(torch, pfb, dev, reps, rounds):
     `rounds` windows of `reps` calls of each side, alternating A and B in one process, after a
     warm-up of both.  One line per case with the median, min, max and quartiles of each side's
     per-call time.  stays_fused: B's median lies below A's by more than the larger of the two
-    sides' interquartile spreads."""
+    sides' interquartile spreads.
+    The SKA-Mid rows (the 4096-point row FFT storing the section) have a second comparison side
+    when `parent_lib` names a library built from the parent commit: P, that library's own to-DADA
+    call on a plan of its own (what a caller of the same entry point had before), alternated with
+    A and B in the same windows; those rows stay fused only if B lies below both A and P by more
+    than the largest interquartile spread of the three."""
     from ctypes import byref, c_int64, c_void_p
     from ska_pst_dsp_model_amd import _lib
     lib = _lib.load()
+    plib = _lib.load(parent_lib) if parent_lib else None
     g = torch.Generator(device=dev).manual_seed(5)
     taps87 = pfb.design_PFB_FIR_filter(256, "8/7", 12)
     taps_pst = pfb.read_fir_filter_coeff(os.path.join(pfb.config.config_dir, "PST_filtertaps.txt"))
@@ -406,8 +415,8 @@ def dada_output(torch, pfb, dev, reps, rounds):
     cases = [c2 + (0, nbit, n_pol) for nbit in (8, 16, 32) for n_pol in (1, 2)]
     cases += [c2 + (nbit, nbit, n_pol) for nbit in (16, 8) for n_pol in (1, 2)]
     cases.append(("LowCBF PST filterbank", taps_pst, 256, "4/3", "polyphase_analysis_lowcbf", 1 << 24, 16, 16, 2))
-    cases.append(("SKA-Mid stage 1 4096ch 8/7 padded", taps_mid, 4096, "8/7", "polyphase_analysis_padded",
-                  1 << 26, 0, 16, 1))
+    mid = ("SKA-Mid stage 1 4096ch 8/7 padded", taps_mid, 4096, "8/7", "polyphase_analysis_padded", 1 << 26)
+    cases += [mid + c for c in ((0, 16, 1), (0, 16, 2), (0, 8, 1), (0, 32, 1), (16, 16, 1))]
     dts = {8: torch.int8, 16: torch.int16, 32: torch.float32}
     for shape, taps, N, os_, variant, n, in_nbit, nbit, n_pol in cases:
         plan = pfb.AnalysisPlan(taps, N, os_, variant, n_pol)
@@ -457,18 +466,48 @@ def dada_output(torch, pfb, dev, reps, rounds):
                                                             c_void_p(sec_b.data_ptr()), nbit, scale, nbytes,
                                                             byref(n_out), stream))
 
+        # P: the parent commit's library, its own plan and section
+        side_p, pplan, sec_p = None, None, None
+        if plib is not None and N == 4096:
+            arr, ptr = _lib.c_double_array(plan.taps)
+            desc = _lib.AnalysisDesc(_lib.PFB_ANALYSIS_PADDED, N, plan.os_factor.nu, plan.os_factor.de, ptr, len(arr),
+                                     n_pol, 0)
+            pplan = c_void_p()
+            assert plib.pfb_analysis_plan_create(byref(desc), byref(pplan)) == 0, plib.pfb_last_error()
+            sec_p = torch.empty_like(sec_a)
+
+            def side_p():
+                if in_nbit:
+                    st = plib.pfb_analysis_execute_dada_to_dada(
+                        pplan, c_void_p(src.data_ptr()), in_nbit, 2, _lib.PFB_DADA_TFP, n, c_void_p(sec_p.data_ptr()),
+                        nbit, scale, nbytes, byref(n_out), stream)
+                else:
+                    st = plib.pfb_analysis_execute_to_dada(pplan, c_void_p(src.data_ptr()), n, n,
+                                                           c_void_p(sec_p.data_ptr()), nbit, scale, nbytes,
+                                                           byref(n_out), stream)
+                assert st == 0, plib.pfb_last_error()
+
         side_a()
         side_b()
         path_in, path = plan.last_dada_input(), plan.last_dada_output()
         torch.cuda.synchronize()
         assert n_out.value == K and torch.equal(sec_a, sec_b), f"dada_output {shape} {in_nbit}->{nbit}: sections differ"
+        sides = [side_a, side_b]
+        parent_path = None
+        if side_p:
+            side_p()
+            torch.cuda.synchronize()
+            parent_path = {0: "none", 1: "fused", 2: "staged"}[int(plib.pfb_analysis_last_dada_output(pplan))]
+            assert n_out.value == K and torch.equal(sec_a, sec_p), f"dada_output {shape}: the parent's section differs"
+            sides.append(side_p)
         for _ in range(2):
-            timeit(torch, side_a, reps)
-            timeit(torch, side_b, reps)
-        ta, tb = [], []
+            for f in sides:
+                timeit(torch, f, reps)
+        times = [[] for _ in sides]
         for _ in range(rounds):
-            ta.append(timeit(torch, side_a, reps))
-            tb.append(timeit(torch, side_b, reps))
+            for t, f in zip(times, sides):
+                t.append(timeit(torch, f, reps))
+        ta, tb = times[0], times[1]
 
         def stats(t):
             q = np.percentile(t, [0, 25, 50, 75, 100])
@@ -477,6 +516,16 @@ def dada_output(torch, pfb, dev, reps, rounds):
         iqr_a, iqr_b = a["q75"] - a["q25"], b["q75"] - b["q25"]
         esz_in, esz = (2 * in_nbit // 8 if in_nbit else 8), 2 * nbit // 8
         prod = K * C * 8
+        extra = {}
+        stays = bool(path == "fused" and a["median"] - b["median"] > max(iqr_a, iqr_b))
+        if side_p:
+            pst = stats(times[2])
+            iqr = max(iqr_a, iqr_b, pst["q75"] - pst["q25"])
+            stays = bool(path == "fused" and min(a["median"], pst["median"]) - b["median"] > iqr)
+            extra = {"P_parent_execute_to_dada_ms": pst, "P_iqr_ms": round(pst["q75"] - pst["q25"], 4),
+                     "parent_path": parent_path, "B_below_P_by_ms": round(pst["median"] - b["median"], 4),
+                     "B_over_P": round(b["median"] / pst["median"], 4)}
+            plib.pfb_analysis_plan_destroy(pplan)
         print(json.dumps({
             "kernel": "dada_output", "shape": shape, "samples": n, "n_pol": n_pol,
             "in": f"nbit{in_nbit}" if in_nbit else "cf32", "nbit": nbit, "path": path, "input_path": path_in,
@@ -486,13 +535,13 @@ def dada_output(torch, pfb, dev, reps, rounds):
             "A_spread_ms": round(a["max"] - a["min"], 4),
             "B_below_A_by_ms": round(a["median"] - b["median"], 4),
             "B_over_A": round(b["median"] / a["median"], 4),
-            "stays_fused": bool(path == "fused" and a["median"] - b["median"] > max(iqr_a, iqr_b)),
+            "stays_fused": stays, **extra,
             # A: the input, the product written, read and rewritten scaled, read again, the section
             "A_bytes": int(n_pol * (n * esz_in + 4 * prod + K * C * esz)),
             "A_bytes_without_scale_pass": int(n_pol * (n * esz_in + 2 * prod + K * C * esz)),
             "B_bytes": int(n_pol * (n * esz_in + (K * C * esz if path == "fused" else 2 * prod + K * C * esz)))}),
             flush=True)
-        del plan, src, cf, scaled, sec_a, sec_b
+        del plan, src, cf, scaled, sec_a, sec_b, sec_p
         torch.cuda.empty_cache()
 
 

@@ -890,7 +890,14 @@ bool analysis_reads_dada(const AnalysisArgs& a, int nbit) {
 
 bool analysis_writes_dada(const AnalysisArgs& a, int nbit) {
   if (nbit != 8 && nbit != 16 && nbit != 32) return false;
-  return stream_shape(a) && knob("PFB_ANALYSIS_NO_STREAM") == nullptr;
+  if (stream_shape(a)) return knob("PFB_ANALYSIS_NO_STREAM") == nullptr;
+  // the generic path's 4096-point row FFT (row_fft4096_pair_dadaout_kernel): the plain product
+  // of one launch over all the call's rows.  (A padded call's shift spans its K_total rows; a
+  // Bunton stream call computes just the rows it keeps, K < K_total, and has no shift.)
+  bool fused = false;
+  if (a.N != 4096 || a.variant == kLowCbf || !analysis_supported(a.N, a.P, a.variant, &fused) || fused) return false;
+  if (a.z || a.out_rs != 0 || a.row0 != 0 || (a.variant == kPadded && a.K != a.K_total)) return false;
+  return (int64_t)a.N * a.n_pol * (nbit / 4) <= kRsrcMaxBytes;  // one row of the section per descriptor
 }
 
 bool analysis_takes_offset(const AnalysisArgs& a) {
@@ -940,7 +947,9 @@ hipError_t launch_analysis(const AnalysisArgs& a, hipStream_t s) {
     }
   }
   if (!a.scratch && !a.z) return hipErrorInvalidValue;
-  if (a.z_stage != 0 && !a.z) return hipErrorInvalidValue;
+  // (z_stage: the two launches apart — with stage-1 rows, or with a DADA product, whose FIR and
+  // storing row FFT analysis_run times as launches of their own)
+  if (a.z_stage != 0 && !a.z && !a.dout) return hipErrorInvalidValue;
   // strided product: padded plans, one launch over all the call's rows, scratch path
   if (a.out_rs > 0 && (a.variant != kPadded || a.z || a.row0 != 0 || a.K != a.K_total || a.out_cs <= 0 ||
                        a.out_keep > a.K_total))
@@ -958,7 +967,7 @@ hipError_t launch_analysis(const AnalysisArgs& a, hipStream_t s) {
     e = hipGetLastError();
   }
   if (e != hipSuccess) return e;
-  if (a.z && a.z_stage == 1) return hipSuccess;
+  if (a.z_stage == 1) return hipSuccess;
   if (a.z) {
     // round trip: the channelised rows come from the Z rows (already in output-row order,
     // N^2 x the FIR sums, index-reversed for the padded variant): the same row FFT on
@@ -984,6 +993,17 @@ hipError_t launch_analysis(const AnalysisArgs& a, hipStream_t s) {
     r.sel_split = a.sel_split;
     r.sel_shift = a.sel_shift;
     r.sel_n = a.sel_n;
+    r.out_keep = a.out_keep;
+  }
+  if (a.dout) {
+    // the row FFT stores the section itself (analysis_writes_dada held above: N = 4096, one
+    // launch over all the call's rows): output rows t < out_keep from the scratch rows
+    r.dout = a.dout;
+    r.dout_nbit = a.dout_nbit;
+    r.dout_scale = a.dout_scale;
+    r.n_pol = a.n_pol;
+    r.out = nullptr;
+    r.n_total = rows;
     r.out_keep = a.out_keep;
   }
   if (a.variant == kBunton) return dispatch_row_fft<-1>(a.N, r, a.n_pol, s);

@@ -133,6 +133,7 @@ static pfb::AnalysisArgs analysis_args(const pfb_analysis_plan* p, const AnaLaun
     a.dout = l.dada_out->base;
     a.dout_nbit = l.dada_out->nbit;
     a.dout_scale = l.dada_out->scale;
+    a.out_keep = l.dada_keep >= 0 ? l.dada_keep : l.K_end;
   }
   a.sds = p->sds;
   a.taps = p->taps.as<float>();
@@ -236,6 +237,20 @@ pfb_status pfb::host::analysis_run(pfb_analysis_plan* p, const AnaLaunch& l, hip
   const double cls_bytes = l.z_stage == 1 ? (double)p->n_pol * 8.0 * in_samples + zrow_bytes
                            : l.z_stage == 2 ? 2.0 * zrow_bytes : bytes;
   ProfScope ps(cls, cls_bytes, s, p->fused || l.z_stage != 0);
+  if (od && !p->fused) {
+    // a section from the generic path (a 4096-channel plan): its two launches apart, each timed
+    // alone as the class that names it — the FIR (4; it reads the section dd in place) and the
+    // row FFT that stores the section (5: the scratch rows in, the kept rows' samples out)
+    a.z_stage = 1;
+    {
+      ProfScope fir(4, (double)p->n_pol * in_b * in_samples + zrow_bytes, s);
+      HIPCHK(pfb::launch_analysis(a, s));
+    }
+    a.z_stage = 2;
+    ProfScope rowfft(5, zrow_bytes + (double)p->n_pol * out_b * a.out_keep * p->N, s);
+    HIPCHK(pfb::launch_analysis(a, s));
+    return PFB_OK;
+  }
   if (dd && !p->fused) {
     // the FIR of the N > 256 path reads the section: timed alone as class 4, which names it
     ProfScope fir(4, (double)p->n_pol * in_b * in_samples + zrow_bytes, s);
@@ -420,7 +435,7 @@ struct QinCall {
 // the plan is on the streaming kernel (the FUSED side's kernel; section_kernel_shape's LowCBF rule)
 static bool analysis_on_stream_kernel(const pfb_analysis_plan* p) {
   pfb::AnalysisArgs a;
-  return section_kernel_shape(p, a) && pfb::analysis_writes_dada(a, 32);
+  return section_kernel_shape(p, a) && pfb::analysis_takes_offset(a);
 }
 
 // the one-shot passes read such a section where it lies (else it is unpacked first)
@@ -911,7 +926,16 @@ static pfb_status filterbank_exec(pfb_analysis_plan* p, const pfb_cf32* in, int6
   if (Kt > 0) {
     // straight into the caller's buffer where fb_rows_dst finds room, else through the staging
     // buffer and a copy (round 6: the SKA-Mid cascade's stage 2 lost a 244-us copy per call)
-    pfb_status st = fb_rows_dst(p, l, (float2*)out, out_ps, cap, Krun, mem == PFB_MEM_HOST);
+    // (a section: the launch stores the Kt kept rows itself — of a padded call's K computed
+    // rows, rows [Kt, K) are not made — so there is no staging buffer and no copy)
+    pfb_status st = PFB_OK;
+    if (od) {
+      l.out = (float2*)out;
+      l.out_ps = out_ps;
+      l.dada_keep = Kt;
+    } else {
+      st = fb_rows_dst(p, l, (float2*)out, out_ps, cap, Krun, mem == PFB_MEM_HOST);
+    }
     if (st != PFB_OK) return st;
     l.in = w;
     l.in_ps = wps;
@@ -1034,9 +1058,10 @@ static pfb_status analysis_to_dada(pfb_analysis_plan* p, const pfb_cf32* in, int
   DadaSection sec{};
   if (sec_in) {
     sec = *sec_in;
-    // (the DADA-store kernels read cf32, a section of the output's NBIT, or an integer
-    // section when they write NBIT 32)
-    if (fused && !pfb::dadaout_reads_dada(sec.nbit, nbit)) sec.force_staged = true;
+    // (the streaming DADA-store kernels read cf32, a section of the output's NBIT, or an integer
+    // section when they write NBIT 32.  A 4096-channel plan's FIR reads the section and its row
+    // FFT stores the other one, in launches of their own: any pair of NBITs)
+    if (fused && analysis_on_stream_kernel(p) && !pfb::dadaout_reads_dada(sec.nbit, nbit)) sec.force_staged = true;
   }
   const DadaSection* sp = sec_in ? &sec : nullptr;
   pfb_status st;
@@ -1127,8 +1152,9 @@ static pfb_status analysis_quantised(pfb_analysis_plan* p, const pfb_cf32* in, i
       return fail(PFB_ERR_BUFFER_TOO_SMALL, "output capacity %lld < %lld bytes", (long long)cap_bytes,
                   (long long)need);
   }
-  pfb::AnalysisArgs shape;
-  const bool fusable = section_kernel_shape(p, shape) && pfb::analysis_writes_dada(shape, 32);
+  // (the moments instantiation is the streaming kernel's: a 4096-channel plan, whose row FFT
+  // stores a plain section itself, has none)
+  const bool fusable = analysis_on_stream_kernel(p);
   if (p->quant_mode == PFB_QUANTISER_MOMENTS_FUSED && !fusable)
     return fail(PFB_ERR_UNSUPPORTED, "quantiser moments FUSED: the plan is not on the streaming analysis kernel");
   const bool fused = fusable && p->quant_mode != PFB_QUANTISER_MOMENTS_STAGED;

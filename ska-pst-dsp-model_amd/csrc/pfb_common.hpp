@@ -429,6 +429,15 @@ struct RowFftArgs {
   int out_rs = 0, out_cs = 0;
   int sel_split = 0, sel_shift = 0, sel_n = 0;
   int64_t out_keep = 0;
+  // the product goes out as a DADA section instead of `out` (AnalysisArgs::dout; the 4096-point
+  // row_fft4096_pair_dadaout_kernel only): row t, bin c, polarisation p at byte
+  // ((t 4096 + c) n_pol + p) dout_nbit / 4, each component to_sample(dout_scale * x) of the x
+  // the cf32 store writes.  row_base 0, n_rows = n_total, no perm / gain / runs; rows
+  // t < out_keep are made, from the input rows (t + sds) mod n_total when remap is set
+  void* dout = nullptr;
+  int dout_nbit = 0;
+  float dout_scale = 1.f;
+  int n_pol = 1;
 };
 
 template <int N>

@@ -329,8 +329,11 @@ struct AnaLaunch {
   // the launch reads the section instead of `in` (analysis_dada_fusable plans only)
   const AnaDada* dada_in = nullptr;
   // the launch writes the section instead of `out`, which is ignored
-  // (analysis_dada_out_fusable plans only)
+  // (analysis_dada_out_fusable plans only).  dada_keep: the rows of it that exist — a padded
+  // stream call computes K_end = K rows for the circular shift and returns Kt; shifted rows
+  // [Kt, K) are not made (AnalysisArgs::out_keep); negative: all K_end rows
   const AnaOut* dada_out = nullptr;
+  int64_t dada_keep = -1;
   // the launch stores the plain cf32 product and its moments (streaming-kernel plans only)
   AnaMoments* moments = nullptr;
   // the launch rounds its new samples at the load (the input quantiser, FUSED: streaming-kernel

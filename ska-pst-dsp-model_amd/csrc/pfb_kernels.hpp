@@ -114,7 +114,9 @@ struct AnalysisArgs {
   // ((k C + c) n_pol + p) dout_nbit / 4 of dout, C = N (216 for the LowCBF instantiation), its
   // value to_sample(dout_scale * x) per component of the x the cf32 kernel stores.  dout is
   // aligned to one complex sample; `out` and out_pol_stride are unused.  A DADA input (din)
-  // has the same NBIT, or dout_nbit is 32 (dadaout_reads_dada).
+  // has the same NBIT, or dout_nbit is 32 (dadaout_reads_dada) — the streaming kernel's rule;
+  // on the generic path (N = 4096) the FIR reads din and the row FFT stores dout, any pair of
+  // NBITs, and only the output rows below out_keep are made.
   void* dout = nullptr;
   int dout_nbit = 0;
   float dout_scale = 1.f;
@@ -131,7 +133,9 @@ struct AnalysisArgs {
 // the plan's kernel has a loader for such a section (the streaming kernel; the LDS-shared FIR
 // of the N > 256 path, launches without stage-1 rows)
 bool analysis_reads_dada(const AnalysisArgs& a, int nbit);
-// the plan's kernel has a DADA store (the streaming kernel)
+// the plan's kernel has a DADA store: the streaming kernel, or — N = 4096, the plain product
+// of one launch over all the call's rows (row0 0; padded: K = K_total) — the generic path's
+// row FFT (row_fft4096_pair_dadaout_kernel, which makes the output rows below a.out_keep)
 bool analysis_writes_dada(const AnalysisArgs& a, int nbit);
 // the streaming kernel with the DADA store (pfb_ana_stream_dadaout.hip); lcbf: the LowCBF
 // instantiation (launch_lowcbf_stream's shape)
